@@ -11,8 +11,15 @@ synthetic data rows sharded N/S, the n particles sharded n/S per GPU.
 One step = exchange + scores + median (exact radix select over n^2 distances)
 + phi (K.[X|S] on MFMA) + x += eps*phi for all n particles.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(metric, value, unit, ms_per_step, ...).  --dump-outputs DIR then writes what
+the last timed step left a caller with (dump_outputs below).  Everything else
+-- the roofline of phi_mm, the per-stage breakdown on extra steps, the passes
+against their bounds, the multi-GPU report and the CPU baseline -- is added to
+the line by --full only.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment
 launches its N ranks itself (a torch.distributed.run child on 127.0.0.1,
@@ -21,12 +28,12 @@ one-Process-per-rank launch, experiments/logreg.py:126-140) and relays rank
 0's line.  Every rank checks that the process group has exactly --gpus ranks.
 
 Prints ONE JSON line (rank 0).  value = n*K / max-over-ranks wall time of the K
-timed steps (whole job).  roofline: the dominant kernel (phi_mm, the fused
+timed steps (whole job).  roofline (--full): the dominant kernel (phi_mm, the fused
 exp + K.[Xc|S] MFMA GEMM) -- algorithmic 4*m*n*d flop per launch / its mean
 HIP-event duration, against the ceiling of the engine it runs on: the
 fp32-accurate fp16-split engine FmtH2 (2516 TF fp16 dense / 3 products = 839
 TF of fp32 products; csrc/gemm_x3.hpp), the bf16-split FmtX3 (/ 6 = 419 TF) or
-the 157.3 TF fp32 MFMA peak (--gemm x3 / f32).  cpu_baseline: the
+the 157.3 TF fp32 MFMA peak (--gemm x3 / f32).  cpu_baseline (--full): the
 reference algorithm's per-pair autograd loop (oracle/loop_baseline.py, a port)
 timed on this host on a bounded sample, rank 0 at N=1 only.
 """
@@ -289,6 +296,42 @@ def multi_gpu_report(sampler, eng, local_stages, world):
             "exchange_ms_per_rank": [r["exchange_ms"] for r in ranks]}
 
 
+DUMP_PARTICLE_BYTES = 32 << 20    # of the 64 MB a dump may hold in all
+
+
+def dump_rows(n, d):
+    """The particle rows a dump keeps: all n while they fit DUMP_PARTICLE_BYTES
+    as float32, else a fixed (seeded) sorted sample of them."""
+    keep = max(1, DUMP_PARTICLE_BYTES // (4 * d))
+    if n <= keep:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+
+
+def dump_outputs(out_dir, sampler, eng, rank, world, n, d):
+    """What the last timed step left its caller with, as float arrays:
+    particles.npy  (rows, d) float32  the particles after the step (every
+                   rank's own block, in global row order; rows = dump_rows)
+    bandwidth.npy  (2,) float64       the step's median squared distance and
+                   the bandwidth h it set (the engine's select state)
+    The inputs are seeded, so two builds given the same arguments write
+    arrays that can be compared entry for entry.  Rank 0 writes."""
+    rows = dump_rows(n, d)
+    m = n // world
+    mine = rows[(rows >= rank * m) & (rows < (rank + 1) * m)] - rank * m
+    own = sampler.particles.detach()[torch.as_tensor(mine, device=sampler.particles.device)]
+    own = own.to(torch.float32).cpu().numpy()
+    if world > 1:
+        blocks = [None] * world
+        dist.all_gather_object(blocks, own)
+        own = np.concatenate(blocks, axis=0)
+    med, h, _ = eng.state.read()
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "particles.npy"), own)
+        np.save(os.path.join(out_dir, "bandwidth.npy"), np.array([med, h], dtype=np.float64))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     ap = argparse.ArgumentParser()
@@ -299,10 +342,16 @@ def main(argv=None):
     ap.add_argument("--particles", type=int, default=65536)
     ap.add_argument("--dim", type=int, default=256)
     ap.add_argument("--data-rows", type=int, default=16384, help="global data rows")
-    ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the roofline, the per-stage breakdown and passes, the "
+                         "multi-GPU exchange report and the CPU baseline (runs of their own)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="with --full")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip it")
     ap.add_argument("--breakdown", type=int, default=3,
-                    help="extra steps after the timed region with every stage's HIP events")
+                    help="with --full: extra steps after the timed region with every stage's "
+                         "HIP events")
     ap.add_argument("--gemm", default="h2", choices=["h2", "x3", "f32"],
                     help="MFMA engine of the contractions (h2: fp16 split, the default)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -310,6 +359,8 @@ def main(argv=None):
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher self-test: ranks form the (gloo) group and report, no GPU work")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, argv)
@@ -375,6 +426,9 @@ def main(argv=None):
     # kernels); every other stage's pair of stream markers would stall the
     # queue between kernels (≈ 10 µs each, profiles/r13j), so the per-stage
     # breakdown is timed on --breakdown extra steps after the timed region
+    # (--full).  A plain run keeps phi_mm's events too: they are part of the
+    # timed path that `value` has always measured (with a timer set the step
+    # launches its kernels itself, it does not replay the warm-up's graph)
     timer = StageTimer(only={"phi_mm"})
     sampler.timer = timer
     barrier()
@@ -391,38 +445,11 @@ def main(argv=None):
                           device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
-    ev = timer.summary().get("phi_mm") or [float("nan")]
-    phi_timed = gather_max({"phi_mm": float(np.mean(ev))}, world, args.backend, dev)
-    full = StageTimer()
-    sampler.timer = full
-    for _ in range(args.breakdown):
-        sampler.make_step(eps)
-    sampler.timer = None
-    local_stages = {k: float(np.mean(v)) for k, v in full.summary().items()}
-    # N > 1: each stage's mean HIP-event time, max over ranks (the exchange
-    # stages allgather_x / allreduce_scores / hist_allreduce included)
-    stages = gather_max(local_stages, world, args.backend, dev)
-    assert bool(torch.isfinite(sampler._work).all()), "non-finite particles"
-
-    m = n // world
-    phi_ms = phi_timed["phi_mm"]     # the timed region's own launches
     eng = sampler._engines[next(iter(sampler._engines))]
-    gemm = eng.phi_gemm
-    peak, peak_basis = engine_peak(gemm)
-    # the committed PMC summary is an N=1 profile: only quoted for the N=1 run
-    # phi_mm is the NN tile with the fused exp (<TN, DMA, EXP=true, ..., Fmt>);
-    # the logreg G.Xd launch is the same tile with EXP=false
-    from dsvgd import _native as NL
-    symrow = NL.load().dsvgd_phi_set_symrow(1)       # read the form back (set returns it)
-    NL.load().dsvgd_phi_set_symrow(symrow)
-    knames = {"h2": ((["_ZN5dsvgd13phi_w1_kernelILi4E"] if symrow else
-                      ["_ZN5dsvgd13phi_w1_kernelILi1E", "_ZN5dsvgd13phi_w1_kernelILi2E"])
-                     if eng.sym else ["_ZN5dsvgd13phi_w1_kernelILi0E"]),
-              "x3": ["void dsvgd::nn_x3_kernel<4, true, true, true, 2, dsvgd::FmtX3,"],
-              "f32": ["void dsvgd::nn_kernel<4, true,"]}[gemm]
-    traffic, traffic_src = pmc_traffic(knames) if world == 1 else (None, None)
-    flops = 4.0 * m * n * d
-    achieved = flops / (phi_ms * 1e-3) / 1e12
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sampler, eng, rank, world, n, d)
+    assert bool(torch.isfinite(sampler._work).all()), "non-finite particles"
+    m = n // world
     out = {
         "metric": "SVGD particle-updates/sec (n=65536,d=256) at 1/2/4/8 GPUs + % MFMA/HBM roofline",
         "value": n * args.steps / el,
@@ -445,6 +472,61 @@ def main(argv=None):
         "config": {"workload": "dist-logreg DistSampler all_scores, Jacobi, median bandwidth",
                    "n": n, "d": d, "N_global": Ng, "parallelism": "dp%d" % world,
                    "particles_per_gpu": m},
+        "gemm": eng.phi_gemm,
+        "phi_splits": int(eng.splits),
+        "process_group": {"backend": args.backend if world > 1 else None,
+                          "world_size_seen": dist.get_world_size() if world > 1 else 1},
+    }
+    if args.full:
+        out.update(full_report(args, sampler, eng, timer, el, (xl, tl), rank, world, dev))
+        out["process_group"]["stages"] = ("mean per step, max over ranks" if world > 1
+                                          else "mean per step")
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+    return 0
+
+
+def full_report(args, sampler, eng, timer, el, data_local, rank, world, dev):
+    """--full: what rides on the headline line besides the headline -- the
+    roofline of phi_mm (its HIP events over the timed steps), every stage's
+    time on --breakdown extra steps, the passes against their bounds, the
+    multi-GPU report and the CPU baseline."""
+    from dsvgd.engine import StageTimer
+    n, d = args.particles, args.dim
+    m, per_data, eps = n // world, args.data_rows // world, 1e-4
+    ev = timer.summary().get("phi_mm") or [float("nan")]
+    phi_timed = gather_max({"phi_mm": float(np.mean(ev))}, world, args.backend, dev)
+    full = StageTimer()
+    sampler.timer = full
+    for _ in range(args.breakdown):
+        sampler.make_step(eps)
+    sampler.timer = None
+    local_stages = {k: float(np.mean(v)) for k, v in full.summary().items()}
+    # N > 1: each stage's mean HIP-event time, max over ranks (the exchange
+    # stages allgather_x / allreduce_scores / hist_allreduce included)
+    stages = gather_max(local_stages, world, args.backend, dev)
+    assert bool(torch.isfinite(sampler._work).all()), "non-finite particles"
+
+    phi_ms = phi_timed["phi_mm"]     # the timed region's own launches
+    gemm = eng.phi_gemm
+    peak, peak_basis = engine_peak(gemm)
+    # the committed PMC summary is an N=1 profile: only quoted for the N=1 run
+    # phi_mm is the NN tile with the fused exp (<TN, DMA, EXP=true, ..., Fmt>);
+    # the logreg G.Xd launch is the same tile with EXP=false
+    from dsvgd import _native as NL
+    symrow = NL.load().dsvgd_phi_set_symrow(1)       # read the form back (set returns it)
+    NL.load().dsvgd_phi_set_symrow(symrow)
+    knames = {"h2": ((["_ZN5dsvgd13phi_w1_kernelILi4E"] if symrow else
+                      ["_ZN5dsvgd13phi_w1_kernelILi1E", "_ZN5dsvgd13phi_w1_kernelILi2E"])
+                     if eng.sym else ["_ZN5dsvgd13phi_w1_kernelILi0E"]),
+              "x3": ["void dsvgd::nn_x3_kernel<4, true, true, true, 2, dsvgd::FmtX3,"],
+              "f32": ["void dsvgd::nn_kernel<4, true,"]}[gemm]
+    traffic, traffic_src = pmc_traffic(knames) if world == 1 else (None, None)
+    flops = 4.0 * m * n * d
+    achieved = flops / (phi_ms * 1e-3) / 1e12
+    out = {
         "roofline": {"bound": "mfma",
                      "kernel": {"h2": (("phi_mm (phi_w1_kernel<4>: one launch, each row block's "
                                         "split-K slices walking contiguous K ranges, its transposed "
@@ -477,22 +559,13 @@ def main(argv=None):
         "stages_basis": "mean HIP-event time per step over %d steps after the timed region "
                         "(phi_mm in roofline: the timed steps' own)" % args.breakdown,
         "passes": passes(eng, stages, m, n, d, per_data, args.gemm),
-        "gemm": gemm,
         "step_6n2d_f32_mfma_frac": (6.0 * m * n * d) / (el / args.steps) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-        "phi_splits": int(eng.splits),
-        "process_group": {"backend": args.backend if world > 1 else None,
-                          "world_size_seen": dist.get_world_size() if world > 1 else 1,
-                          "stages": "mean per step, max over ranks" if world > 1 else "mean per step"},
     }
     if world > 1:
         out["multi_gpu"] = multi_gpu_report(sampler, eng, local_stages, world)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(n, d, xl, tl, args.cpu_budget)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
-    return 0
+        out["cpu_baseline"] = cpu_baseline(n, d, data_local[0], data_local[1], args.cpu_budget)
+    return out
 
 
 if __name__ == "__main__":

@@ -12,7 +12,7 @@ for w in $WHAT; do
   case $w in
     probe) timeout -k 10 240 python scripts/phi_probe.py --configs h2:sym,h2:full > $OUT/probe.log 2>&1 || exit 1; grep -v amdgpu.ids $OUT/probe.log ;;
     rank) timeout -k 10 300 python scripts/rank_shape_timing.py --shards ${SHARDS:-1,8} > $OUT/rank.log 2>&1 || exit 1; grep shards $OUT/rank.log ;;
-    bench) timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1 || exit 1; tail -1 $OUT/bench.log | cut -c1-600 ;;
+    bench) timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1 || exit 1; tail -1 $OUT/bench.log | cut -c1-600 ;;
   esac
 done
 for w in $WHAT; do

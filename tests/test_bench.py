@@ -83,7 +83,8 @@ def test_bench_rejects_world_size_mismatch():
 def test_bench_self_launch_two_ranks_gloo():
     """`python bench.py --gpus 2` (the driver's form) measures two ranks."""
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--particles", "4096", "--dim", "64", "--data-rows", "1024", "--backend", "gloo"]
+           "--particles", "4096", "--dim", "64", "--data-rows", "1024", "--backend", "gloo",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -107,7 +108,7 @@ def test_bench_two_ranks_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29763", "bench.py", "--gpus", "2",
            "--steps", "2", "--warmup", "1", "--particles", "8192", "--dim", "256",
-           "--data-rows", "1024", "--backend", "gloo"]
+           "--data-rows", "1024", "--backend", "gloo", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -128,3 +129,74 @@ def test_bench_two_ranks_gloo():
             assert k in ex and ex[k] >= 0.0
     assert out["roofline"]["traffic"] is None   # N=1 PMC summary is not quoted at N>1
     assert "cpu_baseline" not in out
+
+
+def test_dump_rows_fixed_sample():
+    """--dump-outputs keeps every particle row while they fit the budget and
+    else the same sorted sample on every call; the headline shape's dump stays
+    under the 64 MB a dump may hold."""
+    import numpy as np
+
+    import bench
+    assert np.array_equal(bench.dump_rows(4096, 64), np.arange(4096))
+    a, b = bench.dump_rows(65536, 256), bench.dump_rows(65536, 256)
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    assert 0 <= a[0] and a[-1] < 65536 and len(a) < 65536
+    assert len(a) * 256 * 4 + 2 * 8 + 2 * 128 <= 64e6      # both arrays and their .npy headers
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+FULL_ONLY_KEYS = ("roofline", "stages_ms", "passes", "cpu_baseline", "multi_gpu")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A plain run prints the headline line without the --full sections and
+    --dump-outputs writes the particles after the last timed step (float32)
+    and that step's median and bandwidth (float64): the same sampler stepped
+    warmup + steps times in this process arrives at the same arrays."""
+    import numpy as np
+    import torch
+
+    import bench
+    import dsvgd
+    n, d, rows, warm, steps = 4096, 64, 1024, 1, 2
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warm),
+           "--particles", str(n), "--dim", str(d), "--data-rows", str(rows),
+           "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert all(k in out for k in HEADLINE_KEYS) and not any(k in out for k in FULL_ONLY_KEYS)
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    assert abs(out["value"] - n * steps / (out["ms_per_step"] * steps * 1e-3)) < 1e-6 * out["value"]
+    got = np.load(tmp_path / "dump" / "particles.npy")
+    bw = np.load(tmp_path / "dump" / "bandwidth.npy")
+    assert got.dtype == np.float32 and got.shape == (n, d) and np.isfinite(got).all()
+    assert bw.dtype == np.float64 and bw.shape == (2,) and (bw > 0).all()
+
+    x, t = bench.synthetic_data(rows, d - 1)
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    parts = (0.1 * torch.randn(n, d, generator=gen)).to("cuda:0")
+    start = parts.cpu().numpy().copy()
+    sampler = dsvgd.DistSampler(0, 1, dsvgd.targets.LogisticRegression(x, t, gemm="h2"),
+                                dsvgd.RBF("median"), parts, rows, rows,
+                                exchange_particles=True, exchange_scores=True,
+                                include_wasserstein=False, order="jacobi")
+    for _ in range(warm + steps):
+        sampler.make_step(1e-4)
+    torch.cuda.synchronize()
+    want = sampler.particles.cpu().numpy()
+    eng = sampler._engines[next(iter(sampler._engines))]
+    med, h, _ = eng.state.read()
+    # graph replay here, plain launches in the timed steps: phi may differ in
+    # its last bits (1e-3 of the move is generous), and each step's x += eps*phi
+    # rounds once more (one fp32 ulp of the particles' scale per step)
+    moved = np.abs(want - start).max()
+    err = np.abs(got - want).max()
+    tol = (warm + steps) * 2.0 ** -23 * np.abs(want).max() + 1e-3 * moved
+    print("dump vs in-process: err %.3g tol %.3g moved %.3g" % (err, tol, moved))
+    assert moved > 0 and err <= tol
+    assert abs(bw[0] - med) <= 1e-5 * med and abs(bw[1] - h) <= 1e-5 * h
