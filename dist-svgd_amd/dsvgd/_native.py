@@ -176,6 +176,15 @@ SIGNATURES = {
     "dsvgd_phi_partial_reduce": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _p]),
     "dsvgd_phi_finish_parts": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _f,
                                       _f, _p, _i64, _p, _i64, _p, _i64, _p, _int, _p, _i64, _p]),
+    # the kernelized Stein discrepancy (csrc/ksd.hip)
+    "dsvgd_ksd_parts": (_i64, [_i64, _i64, _int]),
+    "dsvgd_ksd_workspace_doubles": (_c.c_size_t, [_i64]),
+    "dsvgd_ksd_gate": (_int, [_p, _i64, _i64, _i64, _p, _p]),
+    "dsvgd_ksd_rows": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _int, _i64, _p,
+                              _p, _p]),
+    "dsvgd_ksd_finish": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p,
+                                _int, _i64, _p, _p, _p, _p, _p]),
+    "dsvgd_ksd_direct": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
 }
 
 

@@ -67,6 +67,12 @@ class SelectState(object):
         o = _SelectState.below_total.offset // 8
         return self.buf[o:o + 3]
 
+    @property
+    def bandwidth(self):
+        """float32[1] device view of h (no synchronisation)."""
+        o = _SelectState.h.offset
+        return self.buf.view(torch.uint8)[o:o + 4].view(torch.float32)
+
     def bracket(self):
         """(lo, hi, below_total, ncand_total, fallback) -- synchronises."""
         raw = self.buf.cpu()
@@ -273,6 +279,8 @@ class PhiEngine(object):
         self.phi = torch.empty(m, d, **f32)
         self.state = SelectState(dev)
         self.plan = None
+        self.score_scale = None   # of the scores in Y (the last pack / pack_scores)
+        self._ksd = None          # ksd()'s workspaces, allocated on first use
         if pair_split is not None:
             self._init_pair_split(*pair_split)
         self.k_rank = (m * n - 1) // 2 if (local_median and m < n) else -1
@@ -328,6 +336,8 @@ class PhiEngine(object):
         before direction(); the distances read only the X half)."""
         assert X.shape == (self.n, self.d)
         s = N.stream(self.device)
+        if S is not None:
+            self.score_scale = float(score_scale)
         with span(self.timer, "pack"):
             self._pack(X, S, score_scale, s)
 
@@ -335,6 +345,7 @@ class PhiEngine(object):
         """Write only the S half of Y (the X half from an earlier pack(X))."""
         assert S.shape == (self.n, self.d)
         s = N.stream(self.device)
+        self.score_scale = float(score_scale)
         with span(self.timer, "pack"):
             N.call("dsvgd_pack_h2", None, self.d, N.ptr(S), N.ld(S), float(score_scale), None,
                    self.n, self.d, self.Y.shape[0], N.ptr(self.Y), self.ldy, None,
@@ -842,6 +853,87 @@ class PhiEngine(object):
         if self.phi_gemm != "h2" or self.d <= self.DIRECT_MAX_D:
             return None
         return bool(float(self.yscale[2 * self.ldy + 2]) != 0.0)
+
+    # --------------------------------------------------------------- KSD --
+    def ksd(self, rows=False, out=None):
+        """Kernelized Stein discrepancy of the particles the last direction()
+        or step() ran on (include/dsvgd.h; DESIGN.md 3, "The KSD diagnostic").  The finish of a step
+        only moves X, so D, Y, KY, rowsum and the bandwidth still describe the
+        pre-update particles: one more sweep over D and an n x d finish.
+
+        Returns a 4-element float64 device tensor [sum_i t_i, sum_i u_ii, V,
+        U] (t_i the off-diagonal row sums of the Stein kernel, V = KSD^2 as a
+        V-statistic, U the unbiased U-statistic; NaN for n = 1), written into
+        `out` if given, without a host sync; with rows=True also the (m,)
+        fp32 row sums t_i.  For a row block (m < n) only the two sums and the
+        rows are meaningful.  The workspaces are allocated on the first call
+        and kept: later calls only launch.
+
+        Needs unscaled scores in Y (score_scale == 1) and the row-block
+        layout (no pair split)."""
+        if self.plan is not None:
+            raise ValueError("ksd() does not support the pair-split layout")
+        if self.score_scale != 1.0:
+            raise ValueError("ksd() needs the scores packed with score_scale == 1.0 (got %r)"
+                             % (self.score_scale,))
+        lib = N.load()
+        s = N.stream(self.device)
+        direct = self.d <= self.DIRECT_MAX_D
+        sym = int(self.sym)
+        key = (direct, sym, self.m)
+        if self._ksd is None or self._ksd["key"] != key:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            W = dict(key=key, out=torch.empty(4, **f64), rows=torch.empty(self.m, **f32),
+                     ws=torch.empty(int(lib.dsvgd_ksd_workspace_doubles(self.m)), **f64))
+            if not direct:
+                W["parts"] = int(lib.dsvgd_ksd_parts(self.m, self.n, sym))
+                W["P"] = torch.empty(W["parts"] * 2 * self.m_pad, **f32)
+                W["a"] = torch.empty(self.n_pad, **f32)
+                W["gate"] = torch.zeros(1, **f32)
+            self._ksd = W
+        W = self._ksd
+        if direct:
+            with span(self.timer, "ksd_direct"):
+                N.call("dsvgd_ksd_direct", N.ptr(self.Y), self.ldy, self.dp, self.d, self.row0,
+                       self.m, self.n, self.state.ptr, N.ptr(W["rows"]), N.ptr(W["ws"]),
+                       N.ptr(W["out"]), s)
+        else:
+            if self.phi_gemm == "h2":
+                # a row whose whole kernel mass is tiny sits below the FmtH2
+                # image of K's absolute precision (include/dsvgd.h,
+                # dsvgd_ksd_gate): phi_mm again on the guard's fallback engine,
+                # gated on a device word -- nothing runs while it reads 0
+                gate = N.ptr(W["gate"])
+                with span(self.timer, "ksd_gate"):
+                    N.call("dsvgd_ksd_gate", N.ptr(self.rowsum), self.splits, self.m, self.n,
+                           gate, s)
+                    if self.Yx3 is None:
+                        N.call("dsvgd_phi_mm_gated", N.ptr(self.D), self.n_pad, N.ptr(self.Y),
+                               self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
+                               N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), gate, s)
+                    else:
+                        N.call("dsvgd_ysplit", N.ptr(self.Y), self.ldy, self.n_pad,
+                               N.ptr(self.Yx3), 0 if self.m16_fb else 1, gate, s)
+                        N.call("dsvgd_phi_mm_x3", N.ptr(self.D), self.n_pad, N.ptr(self.Yx3),
+                               self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
+                               N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), int(sym),
+                               int(self.m16_fb), gate, s)
+            with span(self.timer, "ksd_rows"):
+                N.call("dsvgd_ksd_rows", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
+                       self.dp, self.d, self.row0, self.m, self.n, self.state.ptr, sym,
+                       W["parts"], N.ptr(W["P"]), N.ptr(W["a"]), s)
+            with span(self.timer, "ksd_finish"):
+                N.call("dsvgd_ksd_finish", N.ptr(self.KY), self.ldy, N.ptr(self.rowsum),
+                       self.splits, N.ptr(self.Y), self.ldy, self.dp, self.d, self.row0, self.m,
+                       self.n, self.state.ptr, sym, W["parts"], N.ptr(W["P"]), N.ptr(W["rows"]),
+                       N.ptr(W["ws"]), N.ptr(W["out"]), s)
+        if out is None:
+            out = W["out"].clone()
+        else:
+            assert out.shape == (4,) and out.dtype == torch.float64
+            out.copy_(W["out"])
+        return (out, W["rows"].clone()) if rows else out
 
     # ------------------------------------------------------------ helpers --
     def step(self, X, S, X_own=None, step=0.0, h=None, score_scale=1.0, allreduce=None,

@@ -8,7 +8,13 @@ reference).  The ensemble mean runs in `dsvgd_logreg_predict` (NT MFMA tiles
 + a fixed-order reduction over particle blocks); the reference evaluates it
 in fp64 with numpy, this in fp32, so a test point whose mean probability is
 within ~1e-6 of 0.5 may land on the other side.
+
+`ksd` is the sampler's own convergence measure, for any target: the
+kernelized Stein discrepancy of a particle set (no counterpart in the
+reference; csrc/ksd.hip).
 """
+import math
+
 import torch
 
 from . import _native as N
@@ -19,6 +25,58 @@ def _device_f32(a, dev):
     if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
         t = t.to(device=dev, dtype=torch.float32).contiguous()
     return t
+
+
+def ksd(particles, logp, kernel=None, *, statistic="v", squared=False, device=None):
+    """Kernelized Stein discrepancy (Liu, Lee and Jordan 2016; Chwialkowski et
+    al. 2016) between the particles and the target, for the RBF kernel: a
+    convergence measure that needs only the particles, their scores and the
+    kernel -- the quantity the SVGD direction descends on.
+
+    particles: (n, d) tensor or array; logp: anything a Sampler takes, or an
+    (n, d) tensor / array of precomputed scores grad log p(x_i); kernel:
+    anything a Sampler takes (default RBF("median")).  statistic "v": the
+    V-statistic (1/n^2) sum_ij u_ij (>= 0 up to rounding); "u": the unbiased
+    U-statistic over i != j (may be negative; NaN for n = 1).  Returns a Python
+    float: sqrt(max(., 0)), or the statistic itself with squared=True.
+
+    Runs one engine evaluation on the GPU (PhiEngine.ksd): pack, distances,
+    bandwidth, the K.[Xc | S] product with step 0 and the KSD sweep."""
+    from .engine import PhiEngine
+    from .kernels import RBF, resolve_kernel
+    from .targets import resolve_target
+    if statistic not in ("v", "u"):
+        raise ValueError("statistic must be 'v' or 'u'")
+    X = torch.as_tensor(particles)
+    if X.dim() != 2:
+        raise ValueError("particles must be (n, d), got shape %s" % (tuple(X.shape),))
+    if device is None:
+        device = X.device if X.is_cuda else "cuda"
+    dev = N.require_gpu(device)
+    X = _device_f32(X, dev)
+    n, d = X.shape
+    rbf = resolve_kernel(RBF("median") if kernel is None else kernel, d)
+    scores = None
+    if not callable(logp):
+        scores = torch.as_tensor(logp)
+        if tuple(scores.shape) != (n, d):
+            raise ValueError("precomputed scores must have the particles' shape %s" % ((n, d),))
+    if scores is not None:
+        S = _device_f32(scores, dev)
+    else:
+        S = torch.empty(n, d, dtype=torch.float32, device=dev)
+        resolve_target(logp).score(X, S)
+    eng = PhiEngine(n, d, device=dev)
+    eng.pack(X, S)
+    eng.distances(median=rbf.median)
+    if rbf.median:
+        eng.median_bandwidth()
+    else:
+        eng.fixed_bandwidth(rbf.h)
+    eng.direction(step=0.0, write_phi=False)
+    out = eng.ksd().cpu()
+    val = float(out[2] if statistic == "v" else out[3])
+    return val if squared else math.sqrt(max(val, 0.0))
 
 
 def predictive_prob(particles, x_test):

@@ -14,10 +14,13 @@ Extensions (keyword-only, defaults keep the reference behaviour):
   device              HIP device (default: current cuda device);
   verbose             the reference's per-iteration prints;
   graphs              capture one iteration as a HIP graph and replay it
-                      (built-in targets; default on).
+                      (built-in targets; default on);
+  ksd_every           record the kernelized Stein discrepancy every k-th
+                      timestep into `sampler.diagnostics` (default off).
 The kernel must be RBF-shaped (see dsvgd.kernels); RBF("median") selects the
 median-heuristic bandwidth h = median(D)/log(n), recomputed every iteration.
 """
+import numpy as np
 import pandas as pd
 import torch
 from torch.distributions.normal import Normal
@@ -42,12 +45,24 @@ class Sampler(object):
         self._kernel = kernel
         self._target = resolve_target(logp)
         self._rbf = resolve_kernel(kernel, d)
+        self.diagnostics = None   # sample(ksd_every=k) leaves its KSD records here
 
     def sample(self, n, num_iter, step_size, *, order="sequential", device=None, verbose=True,
-               graphs=True):
-        """Generate samples using SVGD (sampler.py:42-74)."""
+               graphs=True, ksd_every=None):
+        """Generate samples using SVGD (sampler.py:42-74).
+
+        ksd_every=k records the kernelized Stein discrepancy of the particles
+        at timesteps 0, k, 2k, .. <= num_iter, with the bandwidth the sampler
+        used there, into `self.diagnostics` (a DataFrame: timestep, ksd,
+        ksd2_v, ksd2_u, h; ksd = sqrt(max(ksd2_v, 0))), read back once after
+        the loop.  The returned particles do not change by a bit."""
         if order not in ("sequential", "jacobi"):
             raise ValueError("order must be 'sequential' or 'jacobi'")
+        if ksd_every is not None:
+            if isinstance(ksd_every, bool) or int(ksd_every) != ksd_every or ksd_every <= 0:
+                raise ValueError("ksd_every must be a positive integer (or None)")
+            ksd_every = int(ksd_every)
+        self.diagnostics = None
         dev = N.require_gpu(device if device is not None else "cuda")
         q = Normal(0, 1)
         make_sample = lambda: q.sample((self._d, 1))  # noqa: E731  (sampler.py:58-60)
@@ -79,14 +94,47 @@ class Sampler(object):
         # built-in targets are pure kernel launches: capture the iteration
         # once and replay it (user callables run eagerly)
         step = StepGraph(iteration, dev, enabled=graphs and isinstance(target, BuiltinTarget))
+        # KSD records: the Jacobi MFMA step leaves everything ksd() needs
+        # (the launches follow the step, graph replay or not, on the stream);
+        # otherwise a full evaluation on an engine and scores of its own, so
+        # the sampler's buffers and the trajectory are untouched
+        records = list(range(0, num_iter + 1, ksd_every)) if ksd_every else []
+        if records:
+            kout = torch.empty(len(records), 4, dtype=torch.float64, device=dev)
+            kh = torch.empty(len(records), dtype=torch.float32, device=dev)
+            fused = order == "jacobi" and d > PhiEngine.DIRECT_MAX_D
+            keng = engine if fused else PhiEngine(n, d, device=dev)
+            Sk = S if fused else torch.empty_like(S)
+            h_fixed = None if median else self._rbf.h
+
+        def record(l, evaluate):
+            if evaluate:   # (the fused path: the step just ran on these particles)
+                target.score(X, Sk)
+                keng.step(X, Sk, step=0.0, h=h_fixed, write_phi=False)
+            k = l // ksd_every
+            keng.ksd(out=kout[k])
+            kh[k:k + 1].copy_(keng.state.bandwidth)
+
         for l in range(num_iter):
             if verbose:
                 print('Iteration {}'.format(l))
             hist[l].copy_(X)
+            rec = bool(records) and l % ksd_every == 0
+            if rec and not fused:
+                record(l, True)
             step()
+            if rec and fused:
+                record(l, False)
             if verbose:
                 print(X.mean(dim=0).cpu())
         hist[num_iter].copy_(X)
+        if records and num_iter % ksd_every == 0:
+            record(num_iter, True)   # no step follows the last timestep: step 0
+        if records:
+            kv, hv = kout.cpu().numpy(), kh.cpu().numpy()
+            self.diagnostics = pd.DataFrame({
+                "timestep": records, "ksd": np.sqrt(np.maximum(kv[:, 2], 0.0)),
+                "ksd2_v": kv[:, 2], "ksd2_u": kv[:, 3], "h": hv})
         vals = hist.cpu().numpy().reshape(-1, d)
         steps = torch.arange(num_iter + 1).repeat_interleave(n).numpy()
         ids = torch.arange(n).repeat(num_iter + 1).numpy()

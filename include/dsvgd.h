@@ -808,6 +808,71 @@ size_t dsvgd_logreg_predict_workspace_bytes(int64_t n, int64_t Nt, int64_t p);
 int dsvgd_logreg_predict(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Xt,
                          int64_t ldxt, int64_t Nt, float* prob, void* workspace, void* stream);
 
+/* ---- kernelized Stein discrepancy of a Jacobi step's particles ---------
+ * (absent in the reference, whose only diagnostics are the test accuracy of
+ * experiments/logreg_plots.py and the KDE plot of experiments/gmm_plots.py.)
+ * For k = exp(-|x - y|^2 / h) the Stein kernel of the score s is
+ *   u_ij = k_ij [s_i.s_j + (2/h)(s_i - s_j).(x_i - x_j) + 2d/h - (4/h^2) D_ij]
+ * and t_i = sum_{j != i} u_ij splits into what a step leaves behind -- Y =
+ * [Xc | S] (scores unscaled), D, the slices of KY = [K Xc | K S] and rowsum r,
+ * h in st -- plus two weighted row sums over D:
+ *   t_i = s_i.KS_i + (2/h)[r_i a_i - s_i.KXc_i - xc_i.KS_i + b_i]
+ *         + (2d/h) r_i - (4/h^2) q_i,
+ *   a_j = s_j.xc_j,  b_i = sum_{j != i} k_ij a_j,  q_i = sum_{j != i} k_ij D_ij,
+ * and u_ii = |s_i|^2 + 2d/h.  No float atomics anywhere: the same inputs give
+ * the same bits.
+ *
+ * dsvgd_ksd_rows: the one sweep over the owned block of D.  It first forms a
+ * (workspace of roundup(n,128) floats, 16-byte aligned; pads zeroed) from Y
+ * with a small kernel of its own, then writes the partials P: `parts` slots
+ * of [q | b], 2 roundup(m,128) floats each, parts = dsvgd_ksd_parts(m, n,
+ * sym).  Full panel layout (sym = 0; any row0, m <= n): slot z holds column
+ * slice z's sums; pads (+inf) and the element j = row0 + i are masked.
+ * Symmetric layout (sym = 1: m == n, row0 == 0, dsvgd_sqdist_{h2,x3} layout
+ * 1): with T = roundup(n,128)/128 and rparts = parts - T, slot z < rparts
+ * holds the row sums of slice z of each tile row's stored tiles (I, J >= I),
+ * and slot rparts + I the COLUMN sums of the stored off-diagonal tiles of
+ * tile row I, at the rows of J (the terms of the unwritten tile (J, I));
+ * entries of slot rparts + I at rows of tiles J <= I are never written nor
+ * read, a diagonal tile counts once without its diagonal, tiles J < I are
+ * not read. */
+int64_t dsvgd_ksd_parts(int64_t m, int64_t n, int sym);
+int dsvgd_ksd_rows(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t dp, int64_t d,
+                   int64_t row0, int64_t m, int64_t n, const dsvgd_select_state* st, int sym,
+                   int64_t parts, float* P, float* a, void* stream);
+/* t_i and u_ii of the owned rows from the `splits` slices of KY / rowsum
+ * (summed in slice order like dsvgd_phi_finish; the dot products in fp64) and
+ * the slots of P (in slot order); rows[i] = t_i (m floats, nullable); the
+ * sums over the owned rows in fp64 in a fixed two-level order (ws:
+ * dsvgd_ksd_workspace_doubles(m) doubles, one pair per 64 rows); out[0] =
+ * sum_i t_i, out[1] = sum_i u_ii, out[2] = V = (out[0] + out[1]) / n^2,
+ * out[3] = U = out[0] / (n (n - 1)) (NaN for n = 1).  For m < n only
+ * out[0], out[1] and rows are meaningful (a row block's share). */
+size_t dsvgd_ksd_workspace_doubles(int64_t m);
+int dsvgd_ksd_finish(const float* KY, int64_t ldk, const float* rowsum, int64_t splits,
+                     const float* Y, int64_t ldy, int64_t dp, int64_t d, int64_t row0, int64_t m,
+                     int64_t n, const dsvgd_select_state* st, int sym, int64_t parts,
+                     const float* P, float* rows, double* ws, double* out, void* stream);
+/* The FmtH2 image of K (dsvgd_phi_mm_h2: fp16 pairs of 2^15 k) keeps an
+ * absolute 2^-40 per entry, harmless to phi (measured against the self term
+ * k_ii = 1) but not to a row of the KSD whose whole off-diagonal kernel mass
+ * r_i is tiny -- an outlier, a diverging step, a collapsed bandwidth: a row's
+ * KY error is up to n 2^-40 max|Y| against terms of size r_i.  gate[0]
+ * (device float) = 1.0 if an owned row has r_i < n 2^-20 (that error above
+ * ~1e-6 of the row's terms) or NaN, else 0.0; n = 1: 0.0.  The caller then
+ * launches dsvgd_ysplit + dsvgd_phi_mm_x3 (or dsvgd_phi_mm_gated) with this
+ * gate into the same KY / rowsum -- bf16 parts have fp32's exponent range --
+ * before dsvgd_ksd_finish: nothing runs while the gate reads 0. */
+int dsvgd_ksd_gate(const float* rowsum, int64_t splits, int64_t m, int64_t n, float* gate,
+                   void* stream);
+/* d <= 64 (used for d <= 2, beside dsvgd_phi_direct, which leaves no KY):
+ * the same rows and out from explicit differences on the VALU, straight from
+ * Y -- u_ij per pair with D_ij = |x_i - x_j|^2 recomputed; the r x - K X form
+ * cancels at d = 1.  Same ws and second-level reduction as dsvgd_ksd_finish. */
+int dsvgd_ksd_direct(const float* Y, int64_t ldy, int64_t dp, int64_t d, int64_t row0, int64_t m,
+                     int64_t n, const dsvgd_select_state* st, float* rows, double* ws, double* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
