@@ -217,6 +217,116 @@ __global__ __launch_bounds__(256) void scales_h2_kernel(const uint32_t* __restri
   }
 }
 
+// the scales of the one-operand form W = S - t Xc (t = 2 inv_h from the select
+// state; phi_mm's B image over dp columns) from the same pack maxima, in
+// dsvgd_h2_colscale's layout over dp columns: s_c = pow2_scale(b_c) with the
+// bound b_c = max|S_c| + t max|Xc_c| >= max|W_c| (at most 2x loose: one bit of
+// the 22; no pass over Y).  The RANGE GUARD out[2 dp + 2] is at least as
+// conservative as scales_h2_kernel's over all of Y: it fires when that one
+// does, and when max(gS, t gX) > kH2Range min(rS, t rX) -- a row of W whose
+// dominant half sits below the window of the largest entry of either half
+// (g*: the largest magnitude, r*: the smallest nonzero row max of a half).
+__global__ __launch_bounds__(256) void scales_h2w_kernel(const uint32_t* __restrict__ partial,
+                                                         const uint32_t* __restrict__ gmax,
+                                                         int64_t nb, int64_t ldp, int64_t dp,
+                                                         const dsvgd_select_state* __restrict__ st,
+                                                         float* __restrict__ out) {
+  __shared__ uint32_t red[2][16][kScaleCols];
+  __shared__ uint32_t gred[4][4];
+  const int cl = threadIdx.x & (kScaleCols - 1), rg = threadIdx.x / kScaleCols;
+  const int64_t c = (int64_t)blockIdx.x * kScaleCols + cl;
+  const float t = 2.f * st->inv_h;
+  uint32_t mx = 0u, ms = 0u;
+  if (c < dp)
+    for (int64_t b = rg; b < nb; b += 16) {
+      mx = max(mx, partial[b * ldp + c]);
+      ms = max(ms, partial[b * ldp + dp + c]);
+    }
+  red[0][rg][cl] = mx;
+  red[1][rg][cl] = ms;
+  __syncthreads();
+  if (rg == 0 && c < dp) {
+    uint32_t bx = 0u, bs = 0u;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      bx = max(bx, red[0][q][cl]);
+      bs = max(bs, red[1][q][cl]);
+    }
+    const float s = pow2_scale(fmaf(t, __uint_as_float(bx), __uint_as_float(bs)));
+    out[c] = s;
+    out[dp + c] = 1.f / s;
+  }
+  if (blockIdx.x == 0) {
+    uint32_t gx = 0u, gs = 0u, rx = 0x7F800000u, rs = 0x7F800000u;
+    for (int64_t b = threadIdx.x; b < nb; b += 256) {
+      gx = max(gx, gmax[4 * b]);
+      gs = max(gs, gmax[4 * b + 1]);
+      rx = min(rx, gmax[4 * b + 2]);
+      rs = min(rs, gmax[4 * b + 3]);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      gx = max(gx, (uint32_t)__shfl_xor((int)gx, o));
+      gs = max(gs, (uint32_t)__shfl_xor((int)gs, o));
+      rx = min(rx, (uint32_t)__shfl_xor((int)rx, o));
+      rs = min(rs, (uint32_t)__shfl_xor((int)rs, o));
+    }
+    if ((threadIdx.x & 63) == 0) {
+      gred[threadIdx.x >> 6][0] = gx;
+      gred[threadIdx.x >> 6][1] = gs;
+      gred[threadIdx.x >> 6][2] = rx;
+      gred[threadIdx.x >> 6][3] = rs;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float g[4];
+#pragma unroll
+      for (int h = 0; h < 4; ++h)
+        g[h] = __uint_as_float(
+            h < 2 ? max(max(gred[0][h], gred[1][h]), max(gred[2][h], gred[3][h]))
+                  : min(min(gred[0][h], gred[1][h]), min(gred[2][h], gred[3][h])));
+      const float tw = pow2_scale(fmaf(t, g[0], g[1]));
+      out[2 * dp] = tw;
+      out[2 * dp + 1] = 1.f / tw;
+      const bool gx_wide = g[0] > kH2Range * g[2];
+      const bool gs_wide = g[1] > kH2Range * g[3];
+      const bool w_wide = fmaxf(g[1], t * g[0]) > kH2Range * fminf(g[3], t * g[2]);
+      out[2 * dp + 2] = (gx_wide || gs_wide || w_wide) ? 1.f : 0.f;
+    }
+  }
+}
+
+// Wh[kstep][part][column][16 k] = the two fp16 parts of s_c W[16 kstep + k][c],
+// W[r][c] = fmaf(-t, Y[r][c], Y[r][dp + c]) (one rounding), c < dp: the image
+// of ysplit_h2_kernel over dp columns (the same half swap).  Y's padding rows
+// and columns are zero, so the image's are.
+__global__ __launch_bounds__(256) void wsplit_h2_kernel(const float* __restrict__ Y, int64_t ldy,
+                                                        int64_t ksteps, int64_t dp,
+                                                        const dsvgd_select_state* __restrict__ st,
+                                                        const float* __restrict__ colscale,
+                                                        _Float16* __restrict__ Wh) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= ksteps * dp) return;
+  const int64_t kb = t / dp, c = t % dp;
+  const float sc = colscale[c];
+  const float nt = -2.f * st->inv_h;
+  f16x8 s[2][2];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const float* y = Y + (kb * 16 + k) * ldy + c;
+    _Float16 v[2];
+    split_fmt<FmtH2>(sc * fmaf(nt, y[0], y[dp]), v);
+    s[0][k >> 3][k & 7] = v[0];
+    s[1][k >> 3][k & 7] = v[1];
+  }
+  const int sw = (int)((c >> 3) & 1);
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    _Float16* dst = Wh + ((kb * 2 + p) * dp + c) * 16;
+    *reinterpret_cast<f16x8*>(dst + 8 * sw) = s[p][0];
+    *reinterpret_cast<f16x8*>(dst + 8 * (sw ^ 1)) = s[p][1];
+  }
+}
+
 // rscale[i] = pow2_scale(max_c |A[i][c]|) and rinv[i] = 1 / rscale[i] for
 // rows i < rows (1 for a zero / non-finite row; rows_pad > rows: 1): the
 // per-row scales of an NT row image (the Gram's, logreg's W) -- one wave per row.
@@ -530,6 +640,27 @@ int dsvgd_h2_scales(const uint32_t* partial, const uint32_t* gmax, int64_t nb, i
   hipLaunchKernelGGL(scales_h2_kernel, dim3((unsigned)((cols + kScaleCols - 1) / kScaleCols)),
                      dim3(256), 0, (hipStream_t)stream, partial, gmax, nb, ldy, cols, dp, scale);
   return check_launch("scales_h2");
+}
+
+int dsvgd_h2_wscales(const uint32_t* partial, const uint32_t* gmax, int64_t nb, int64_t ldy,
+                     int64_t dp, const dsvgd_select_state* st, float* wscale, void* stream) {
+  DSVGD_REQUIRE(partial && gmax && st && wscale, "null pointer");
+  DSVGD_REQUIRE(nb > 0 && dp > 0 && ldy >= 2 * dp, "sizes");
+  hipLaunchKernelGGL(scales_h2w_kernel, dim3((unsigned)((dp + kScaleCols - 1) / kScaleCols)),
+                     dim3(256), 0, (hipStream_t)stream, partial, gmax, nb, ldy, dp, st, wscale);
+  return check_launch("scales_h2w");
+}
+
+int dsvgd_h2_wsplit(const float* Y, int64_t ldy, int64_t rows, int64_t dp,
+                    const dsvgd_select_state* st, const float* wscale, void* Wh, void* stream) {
+  DSVGD_REQUIRE(Y && st && wscale && Wh, "null pointer");
+  DSVGD_REQUIRE(rows > 0 && rows % kX3Step == 0, "rows must be a positive multiple of 16");
+  DSVGD_REQUIRE(dp > 0 && dp % 16 == 0 && ldy >= 2 * dp, "dp must be a multiple of 16, ldy >= 2 dp");
+  DSVGD_REQUIRE(((uintptr_t)Wh & 15) == 0, "16-byte alignment");
+  const int64_t ksteps = rows / kX3Step, threads = ksteps * dp;
+  hipLaunchKernelGGL(wsplit_h2_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, Y, ldy, ksteps, dp, st, wscale, (_Float16*)Wh);
+  return check_launch("wsplit_h2");
 }
 
 int64_t dsvgd_h2_image_bytes(int64_t rows, int64_t cols) {

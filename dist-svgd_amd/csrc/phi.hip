@@ -15,6 +15,7 @@
 #include "gemm_tiles.hpp"
 #include "gemm_x3.hpp"
 #include "phi_w1.hpp"
+#include "phi_w2.hpp"
 
 namespace dsvgd {
 
@@ -362,6 +363,50 @@ int nn_split_gemm(bool exp_, const float* A, int64_t K, const typename F::E* Yx,
 #undef DSVGD_X3_TN
 }
 
+// phi_mm of the ONE-OPERAND form, K . W with W = S - (2/h) Xc (dp columns, dp
+// a multiple of 256; dsvgd_h2_wsplit's image): half the MFMAs of K . [Xc | S]
+// for the same A staging.  Two tiles (DSVGD_W_TILE, a build-time choice; the
+// other one only in `make ab` builds; DESIGN.md 3 has both times):
+//   1  phi_w1_kernel's 256-column shape (NI = 2: four waves of 128 rows x 64
+//      columns, 128 accumulators, two blocks per CU -- one block's staging
+//      VALU runs beside the other's MFMAs);
+//   2  phi_w2_kernel: 256 rows x 256 columns, four waves of 128 x 128, one
+//      block per CU (48 MFMAs per wave per K-step to hide the staging behind).
+// The symmetric layout in one launch (DS 4), the full layout with a row block
+// by DS 0.
+#ifndef DSVGD_W_TILE
+#define DSVGD_W_TILE 1
+#endif
+constexpr int kWTileRows = DSVGD_W_TILE == 2 ? 256 : 128;
+int nn_h2w_gemm(const float* D, int64_t K, const _Float16* Wh, int64_t dp, int splits,
+                const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
+                int64_t row0, hipStream_t s, int sym, const float* colinv, const float* gate) {
+  const int64_t kchunk = roundup((K + splits - 1) / splits, kX3Step);
+  const dim3 grid((unsigned)(dp / 256), (unsigned)(roundup(m, kWTileRows) / kWTileRows),
+                  (unsigned)splits);
+#if DSVGD_W_TILE == 2
+  const int64_t a_rows = roundup(m, 128);
+  if (sym)
+    hipLaunchKernelGGL((phi_w2_kernel<4>), grid, dim3(PhiW2::kThreads), 0, s, D, K, a_rows, Wh, dp,
+                       K, kchunk, st, C, ldc, rowsum, m, row0, colinv, gate, xmap_ok(grid, 1));
+  else
+    hipLaunchKernelGGL((phi_w2_kernel<0>), grid, dim3(PhiW2::kThreads), 0, s, D, K, a_rows, Wh, dp,
+                       K, kchunk, st, C, ldc, rowsum, m, row0, colinv, gate, xmap_ok(grid, 2));
+  return check_launch("phi_w2_kernel");
+#else
+  if (sym) {
+    hipLaunchKernelGGL((phi_w1_kernel<4, 2, true>), grid, dim3(PhiW1::kThreads), 0, s, D, K, Wh,
+                       dp, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, 0, gate, 0, 0, 0,
+                       0, xmap_ok(grid, 1) ? 1 : 0);
+    return check_launch("phi_w1_kernel(W, rows)");
+  }
+  hipLaunchKernelGGL((phi_w1_kernel<0, 2, true>), grid, dim3(PhiW1::kThreads), 0, s, D, K, Wh, dp,
+                     K, kchunk, st, C, ldc, rowsum, m, row0, 0, colinv, 0, gate, 0, 0, 0, 0,
+                     xmap_ok(grid, 2));
+  return check_launch("phi_w1_kernel(W)");
+#endif
+}
+
 int nn_x3_gemm(bool exp_, const float* A, int64_t K, const __bf16* Yx, int64_t ldy, int splits,
                const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
                int64_t row0, hipStream_t s, int sym, int m16, const float* gate) {
@@ -448,6 +493,88 @@ __global__ __launch_bounds__(256) void phi_finish4_kernel(
 #pragma unroll
     for (int e = 0; e < 4; ++e) x[e] += step * p[e];
     *reinterpret_cast<f32x4*>(X + i * ldx + c) = x;
+  }
+}
+
+// phi_finish of the one-operand form: KW / rowsum hold `splits` partials of
+// K . W (W = S - (2/h) Xc, dp columns, row stride ldk), summed in slice order:
+//   phi[i][c] = inv_n ((s_i + kw) + (2/h) (r_i xc_i)) [+ extra[i][c]]
+// While the range guard word reads nonzero the fallback has filled KY /
+// rowsum with `splits_fb` partials of K . [Xc | S] (row stride ldky) instead:
+// phi_finish_kernel's formula on them, in its order.  V: columns per thread
+// (4: 16-byte accesses, every stride and base aligned; the same bits as 1).
+template <int V>
+__global__ __launch_bounds__(256) void phi_finish_w_kernel(
+    const float* KW, int64_t ldk, const float* __restrict__ rowsum, int splits, const float* KY,
+    int64_t ldky, int splits_fb, const float* __restrict__ Y, int64_t ldy, int64_t row0, int64_t m,
+    int64_t dv, int64_t dp, const dsvgd_select_state* __restrict__ st,
+    const float* __restrict__ guard, float inv_n, float step, const float* __restrict__ extra,
+    int64_t lde, float* __restrict__ phi, int64_t ldphi, float* __restrict__ X, int64_t ldx) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= m * dv) return;
+  const int64_t i = t / dv, c = (t % dv) * V;
+  const float two_inv_h = 2.f * st->inv_h;
+  const int64_t mp = roundup128(m);
+  auto ld = [](const float* q, float (&o)[V]) {
+    if constexpr (V == 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = v[e];
+    } else {
+      o[0] = q[0];
+    }
+  };
+  auto stv = [](float* q, const float (&o)[V]) {
+    if constexpr (V == 4)
+      *reinterpret_cast<f32x4*>(q) = f32x4{o[0], o[1], o[2], o[3]};
+    else
+      q[0] = o[0];
+  };
+  const float* yi = Y + (row0 + i) * ldy;
+  float yx[V], ys[V], p[V];
+  ld(yi + c, yx);
+  ld(yi + dp + c, ys);
+  float r = 0.f;
+  if (*guard != 0.f) {
+    float kx[V] = {}, ks[V] = {}, a[V], b[V];
+    for (int z = 0; z < splits_fb; ++z) {
+      const float* ky = KY + (int64_t)z * m * ldky + i * ldky;
+      ld(ky + c, a);
+      ld(ky + dp + c, b);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        kx[e] += a[e];
+        ks[e] += b[e];
+      }
+      r += rowsum[(int64_t)z * mp + i];
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) p[e] = inv_n * ((ys[e] + ks[e]) + two_inv_h * (r * yx[e] - kx[e]));
+  } else {
+    float kw[V] = {}, a[V];
+    for (int z = 0; z < splits; ++z) {
+      ld(KW + (int64_t)z * m * ldk + i * ldk + c, a);
+#pragma unroll
+      for (int e = 0; e < V; ++e) kw[e] += a[e];
+      r += rowsum[(int64_t)z * mp + i];
+    }
+    // + the self term k_ii w_i' = s_i (x_i - x_i = 0), excluded from phi_mm
+#pragma unroll
+    for (int e = 0; e < V; ++e) p[e] = inv_n * ((ys[e] + kw[e]) + two_inv_h * (r * yx[e]));
+  }
+  if (extra) {
+    float ex[V];
+    ld(extra + i * lde + c, ex);
+#pragma unroll
+    for (int e = 0; e < V; ++e) p[e] += ex[e];
+  }
+  if (phi) stv(phi + i * ldphi + c, p);
+  if (X) {
+    float x[V];
+    ld(X + i * ldx + c, x);
+#pragma unroll
+    for (int e = 0; e < V; ++e) x[e] += step * p[e];
+    stv(X + i * ldx + c, x);
   }
 }
 
@@ -933,6 +1060,19 @@ int64_t phi_splits(int64_t m, int64_t n, int64_t ldy) {
   return s;
 }
 
+// the one-operand form's slices (128-row x 256-column blocks, two per CU):
+// (1) at least two rounds of the 512 resident blocks, (2) every fp32 chain
+// within kMaxChain.  The headline (m = n = 65536, dp = 256): 512 row blocks
+// x 4 slices of 16384 -- 8 | 2048, so the slices map to XCDs (xmap_ok).
+int64_t phi_splits_w(int64_t m, int64_t n, int64_t dp) {
+  const int64_t blocks = (roundup(m, 128) / 128) * std::max<int64_t>(dp / 256, 1);
+  const int64_t n_pad = roundup(n, 128);
+  int64_t s = 1;
+  while (blocks * s < 1024 && n_pad / (2 * s) >= 1024) s *= 2;
+  while (n_pad / s > kMaxChain && s < 64) s *= 2;
+  return s;
+}
+
 }  // namespace dsvgd
 
 using namespace dsvgd;
@@ -940,6 +1080,8 @@ using namespace dsvgd;
 extern "C" {
 
 int64_t dsvgd_phi_splits(int64_t m, int64_t n, int64_t ldy) { return phi_splits(m, n, ldy); }
+
+int64_t dsvgd_phi_splits_w(int64_t m, int64_t n, int64_t dp) { return phi_splits_w(m, n, dp); }
 
 int64_t dsvgd_phi_splits_sym(int64_t n, int64_t ldy) {
   int64_t s = phi_splits(n, n, ldy);
@@ -1079,6 +1221,27 @@ int dsvgd_phi_mm_h2(const float* D, int64_t ldd, const void* Yh, int64_t ldy, in
                 "sym: the symmetric layout needs m == n, row0 == 0, ldy % 256 == 0");
   return nn_h2_gemm(true, D, n_pad, (const _Float16*)Yh, ldy, (int)splits, st, KY, ldk, rowsum, m,
                     row0, (hipStream_t)stream, sym, colinv, gate);
+}
+
+int dsvgd_phi_mm_h2w(const float* D, int64_t ldd, const void* Wh, int64_t ldw, int64_t row0,
+                     int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KW,
+                     int64_t ldk, float* rowsum, int sym, const float* colinv, const float* gate,
+                     void* stream) {
+  DSVGD_REQUIRE(D && Wh && st && KW && rowsum && colinv, "null pointer");
+  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
+  const int64_t n_pad = roundup(n, 128);
+  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
+  DSVGD_REQUIRE(ldw > 0 && ldw % 256 == 0 && ldk >= ldw,
+                "ldw (= dp) must be a multiple of 256, ldk >= ldw");
+  DSVGD_REQUIRE(((uintptr_t)Wh & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
+  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
+  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
+  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
+  DSVGD_REQUIRE(n_pad * ldw * 4 < ((int64_t)1 << 31) && n_pad * 128 * 4 < ((int64_t)1 << 31),
+                "n x ldw too large for 32-bit buffer offsets");
+  DSVGD_REQUIRE(!sym || (m == n && row0 == 0), "sym: the symmetric layout needs m == n, row0 == 0");
+  return nn_h2w_gemm(D, n_pad, (const _Float16*)Wh, ldw, (int)splits, st, KW, ldk, rowsum, m, row0,
+                     (hipStream_t)stream, sym, colinv, gate);
 }
 
 int dsvgd_phi_h2_window(const float* D, int64_t ldd, const void* Yh, int64_t ldy, int64_t row0,
@@ -1282,6 +1445,36 @@ int dsvgd_phi_finish(const float* KY, int64_t ldk, const float* rowsum, int64_t 
                      (hipStream_t)stream, KY, ldk, rowsum, (int)splits, Y, ldy, row0, m, d, dp,
                      st, inv_n, step, extra, lde, phi, ldphi, X, ldx);
   return check_launch("phi_finish");
+}
+
+int dsvgd_phi_finish_w(const float* KW, int64_t ldk, const float* rowsum, int64_t splits,
+                       const float* KY, int64_t ldky, int64_t splits_fb, const float* Y,
+                       int64_t ldy, int64_t row0, int64_t m, int64_t d, int64_t dp,
+                       const dsvgd_select_state* st, const float* guard, float inv_n, float step,
+                       const float* extra, int64_t lde, float* phi, int64_t ldphi, float* X,
+                       int64_t ldx, void* stream) {
+  DSVGD_REQUIRE(KW && KY && rowsum && Y && st && guard, "null pointer");
+  DSVGD_REQUIRE(!extra || lde >= d, "lde");
+  DSVGD_REQUIRE(splits >= 1 && splits <= 1024 && splits_fb >= 1 && splits_fb <= 1024,
+                "splits must be in [1, 1024]");
+  DSVGD_REQUIRE(m > 0 && d > 0 && dp >= d && ldk >= dp && ldky >= 2 * dp && ldy >= 2 * dp, "sizes");
+  DSVGD_REQUIRE(!phi || ldphi >= d, "ldphi");
+  DSVGD_REQUIRE(!X || ldx >= d, "ldx");
+  auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+#define DSVGD_FINISH_W(V, DV)                                                                     \
+  hipLaunchKernelGGL((phi_finish_w_kernel<V>), dim3((unsigned)((m * (DV) + 255) / 256)), dim3(256), \
+                     0, (hipStream_t)stream, KW, ldk, rowsum, (int)splits, KY, ldky,              \
+                     (int)splits_fb, Y, ldy, row0, m, DV, dp, st, guard, inv_n, step, extra, lde, \
+                     phi, ldphi, X, ldx)
+  if (g_phi_finish_vec && d % 4 == 0 && dp % 4 == 0 && ldk % 4 == 0 && ldky % 4 == 0 &&
+      ldy % 4 == 0 && a16(KW) && a16(KY) && a16(Y) && (!extra || (lde % 4 == 0 && a16(extra))) &&
+      (!phi || (ldphi % 4 == 0 && a16(phi))) && (!X || (ldx % 4 == 0 && a16(X)))) {
+    DSVGD_FINISH_W(4, d / 4);
+    return check_launch("phi_finish_w4");
+  }
+  DSVGD_FINISH_W(1, d);
+#undef DSVGD_FINISH_W
+  return check_launch("phi_finish_w");
 }
 
 int dsvgd_phi_direct(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,

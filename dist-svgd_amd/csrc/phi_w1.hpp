@@ -74,8 +74,13 @@ __device__ __forceinline__ f32x4 w1_load_nt(__amdgpu_buffer_rsrc_t r, int voff, 
 // 2: 256-column blocks of 64 columns per wave, 128 accumulators -- two
 // blocks per CU).  EXP = false: f = identity with the FmtH2 A scale (logreg
 // G . Xd, DS 0 only): no exp, no diagonal, no row sums, no select state.
+// (NI = 2 with EXP, the one-operand phi_mm: a register budget of two waves
+// per SIMD -- 128 accumulators leave room, and the second block's MFMAs are
+// what hides this block's staging VALU)
+constexpr int w1_waves(int NI, bool EXP) { return NI == 2 && EXP ? 2 : 1; }
 template <int DS, int NI = 4, bool EXP = true>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void phi_w1_kernel(
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(w1_waves(NI, EXP), w1_waves(NI, EXP)))) void phi_w1_kernel(
     const float* A, int64_t a_npad, const _Float16* Yx, int64_t ldy,
     int64_t K, int64_t kchunk, const dsvgd_select_state* __restrict__ st, float* __restrict__ C,
     int64_t ldc, float* __restrict__ rowsum, int64_t m, int64_t row0, int sym,

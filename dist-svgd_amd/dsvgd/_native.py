@@ -103,6 +103,14 @@ SIGNATURES = {
                                _p, _p, _p]),
     "dsvgd_phi_finish": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _f,
                                 _f, _p, _i64, _p, _i64, _p, _i64, _p]),
+    # the one-operand form of phi_mm: K . (S - (2/h) Xc)
+    "dsvgd_h2_wscales": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "dsvgd_h2_wsplit": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "dsvgd_phi_splits_w": (_i64, [_i64, _i64, _i64]),
+    "dsvgd_phi_mm_h2w": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _int,
+                                _p, _p, _p]),
+    "dsvgd_phi_finish_w": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64,
+                                  _i64, _p, _p, _f, _f, _p, _i64, _p, _i64, _p, _i64, _p]),
     "dsvgd_phi_direct": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _f, _f, _p,
                                 _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
     "dsvgd_phi_row": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _f, _p, _p, _p]),

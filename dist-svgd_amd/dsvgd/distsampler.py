@@ -451,7 +451,8 @@ class DistSampler(object):
             self._engines.clear()      # the old D is freed before the new one is allocated
             self._engines[key] = PhiEngine(
                 n_int, self._d, m=m, row0=row0, device=self._device, local_median=local,
-                pair_split=(self._rank, self._num_shards) if ps else None)
+                pair_split=(self._rank, self._num_shards) if ps else None,
+                phi_form=None if ps else "w")
         eng = self._engines[key]
         eng.set_row0(row0)
         eng.timer = self.timer

@@ -178,7 +178,8 @@ class PhiEngine(object):
     DEFAULT_GEMM = "h2"
 
     def __init__(self, n, d, m=None, row0=0, device=None, local_median=False, gemm=None,
-                 phi_gemm=None, gram_gemm=None, sym_layout=True, pair_split=None):
+                 phi_gemm=None, gram_gemm=None, sym_layout=True, pair_split=None,
+                 phi_form=None):
         """local_median: the median bandwidth is the lower median of the owned
         block's own m x n entries (k = (m n - 1) // 2, h = median / log n) --
         a rank-local bandwidth (the lagged DistSampler modes) -- instead of the
@@ -196,7 +197,14 @@ class PhiEngine(object):
         parts only, direction(p2p=...) exchanges the transposed partials.
         Needs the same scores on every rank, the FmtH2 engines, m = n / S a
         multiple of 256 (of 512 for even S), roundup(d, 32) a multiple of 256 and a bracketed
-        (or fixed) bandwidth -- PhiEngine.pair_split_ok says whether it applies."""
+        (or fixed) bandwidth -- PhiEngine.pair_split_ok says whether it applies.
+
+        phi_form: "xs" (default) runs phi_mm as K . [Xc | S]; "w" as the one
+        dp-wide product K . (S - (2/h) Xc) (half the MFMAs).  "w"
+        engages on the h2 engine with dp % 256 == 0, d > DIRECT_MAX_D, the
+        fused scales and no pair split, else the engine keeps "xs"; the
+        resolved form is `self.phi_form`, fixed for the engine's life.  A "w"
+        engine has no K . Xc, so ksd() raises on it."""
         dev = N.require_gpu(device if device is not None else "cuda")
         lib = N.load()
         m = n if m is None else m
@@ -227,9 +235,23 @@ class PhiEngine(object):
         if gram_gemm != "f32" and self.dp * self.gram_rows * bpe[gram_gemm] >= (1 << 31):
             gram_gemm = "f32"
         self.phi_gemm, self.gram_gemm, self.sym_layout = phi_gemm, gram_gemm, sym_layout
+        # d <= 1024: pack writes the column maxima the scales come from
+        # (dsvgd_pack_h2 / dsvgd_h2_scales); wider, a separate pass over Y
+        self.fused_scales = ("h2" in (phi_gemm, gram_gemm) and self.ldy <= lib.dsvgd_pack_max_ldy()
+                             and d > self.DIRECT_MAX_D)
+        if phi_form not in (None, "xs", "w"):
+            raise ValueError("phi_form must be 'xs' or 'w'")
+        self.phi_form = "w" if (phi_form == "w" and phi_gemm == "h2" and self.dp % 256 == 0
+                                and d > self.DIRECT_MAX_D and self.fused_scales
+                                and pair_split is None) else "xs"
         if phi_gemm == "x3":
             nb = lib.dsvgd_ysplit_bytes(self.n_pad, self.ldy)
             self.Yx = torch.empty(nb // 2, dtype=torch.int16, device=dev)
+        elif phi_gemm == "h2" and self.phi_form == "w":
+            # the image and the scales of W = S - (2/h) Xc, over dp columns
+            nb = lib.dsvgd_h2_image_bytes(self.n_pad, self.dp)
+            self.Wh = torch.empty(nb // 2, dtype=torch.int16, device=dev)
+            self.wscale = torch.empty(2 * self.dp + 3, **f32)
         elif phi_gemm == "h2":
             nb = lib.dsvgd_h2_image_bytes(self.n_pad, self.ldy)
             self.Yx = torch.empty(nb // 2, dtype=torch.int16, device=dev)
@@ -258,10 +280,6 @@ class PhiEngine(object):
                 # full D layout only
                 self.Yx3 = None
                 self.sym_layout = False
-        # d <= 1024: pack writes the column maxima the scales come from
-        # (dsvgd_pack_h2 / dsvgd_h2_scales); wider, a separate pass over Y
-        self.fused_scales = ("h2" in (phi_gemm, gram_gemm) and self.ldy <= lib.dsvgd_pack_max_ldy()
-                             and d > self.DIRECT_MAX_D)
         if self.fused_scales:
             self.colmax_nb = lib.dsvgd_pack_blocks(rows)
             i32 = dict(dtype=torch.int32, device=dev)
@@ -273,8 +291,15 @@ class PhiEngine(object):
         if self.sym and phi_gemm == "h2":
             # the one-launch form (phi_w1 DS 4) walks longer slices
             self.splits = int(lib.dsvgd_phi_splits_sym(n, self.ldy))
-        self.KY = torch.empty(self.splits * m, self.ldy, **f32)
-        self.rowsum = torch.empty(self.splits * self.m_pad, **f32)
+        # (a "w" engine: the range guard's fallback writes KY in the
+        # two-operand layout with these slices, the W product its own count
+        # at row stride dp into the same buffer)
+        self.splits_fb = ky_slices = self.splits
+        if self.phi_form == "w":
+            self.splits = int(lib.dsvgd_phi_splits_w(m, n, self.dp))
+            ky_slices = max(self.splits_fb, -(-self.splits * self.dp // self.ldy))
+        self.KY = torch.empty(ky_slices * m, self.ldy, **f32)
+        self.rowsum = torch.empty(max(self.splits, self.splits_fb) * self.m_pad, **f32)
         self.mean = torch.empty(d, **f32)    # the packing centre (dsvgd_colcenter)
         self.phi = torch.empty(m, d, **f32)
         self.state = SelectState(dev)
@@ -527,6 +552,9 @@ class PhiEngine(object):
                        float(step), ex, lde, phi, self.d, xo, ldx, N.ptr(self.KY),
                        self.KY.numel(), s)
             return
+        if self.phi_form == "w":
+            self._direction_w(inv_n, step, ex, lde, phi, xo, ldx, s)
+            return
         if self.sym and self.phi_gemm == "h2":
             # the slices were sized for the symmetric phi_mm form in force at
             # construction (dsvgd_phi_splits_sym: longer slices for the
@@ -584,6 +612,40 @@ class PhiEngine(object):
         N.call("dsvgd_phi_finish", N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), self.splits,
                N.ptr(self.Y), self.ldy, self.row0, self.m, self.d, self.dp, self.state.ptr,
                float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx, s)
+
+    def _direction_w(self, inv_n, step, ex, lde, phi, xo, ldx, s):
+        """phi_mm in the one-operand form: the scales and the image of W =
+        S - (2/h) Xc (the bandwidth is on the device by now), K . W into KY at
+        row stride dp, and its finish.  The range guard word of the W scales
+        hands the step to today's two-operand fallback instead (the FmtX3
+        image of Y and phi_mm_x3, or the exact f32 phi_mm), gated on the
+        device; the finish reads the same word."""
+        dp, ldy = self.dp, self.ldy
+        guard = N.ptr(self.wscale) + 4 * (2 * dp + 2)
+        with span(self.timer, "ysplit"):
+            N.call("dsvgd_h2_wscales", N.ptr(self.colmax), N.ptr(self.gmax), self.colmax_nb, ldy,
+                   dp, self.state.ptr, N.ptr(self.wscale), s)
+            N.call("dsvgd_h2_wsplit", N.ptr(self.Y), ldy, self.n_pad, dp, self.state.ptr,
+                   N.ptr(self.wscale), N.ptr(self.Wh), s)
+        with span(self.timer, "phi_mm"):
+            N.call("dsvgd_phi_mm_h2w", N.ptr(self.D), self.n_pad, N.ptr(self.Wh), dp, self.row0,
+                   self.m, self.n, self.state.ptr, self.splits, N.ptr(self.KY), dp,
+                   N.ptr(self.rowsum), int(self.sym), N.ptr(self.wscale) + 4 * dp, guard, s)
+        with span(self.timer, "phi_guard"):
+            if self.Yx3 is None:
+                N.call("dsvgd_phi_mm_gated", N.ptr(self.D), self.n_pad, N.ptr(self.Y), ldy,
+                       self.row0, self.m, self.n, self.state.ptr, self.splits_fb, N.ptr(self.KY),
+                       ldy, N.ptr(self.rowsum), guard, s)
+            else:
+                N.call("dsvgd_ysplit", N.ptr(self.Y), ldy, self.n_pad, N.ptr(self.Yx3),
+                       0 if self.m16_fb else 1, guard, s)
+                N.call("dsvgd_phi_mm_x3", N.ptr(self.D), self.n_pad, N.ptr(self.Yx3), ldy,
+                       self.row0, self.m, self.n, self.state.ptr, self.splits_fb, N.ptr(self.KY),
+                       ldy, N.ptr(self.rowsum), int(self.sym), int(self.m16_fb), guard, s)
+        N.call("dsvgd_phi_finish_w", N.ptr(self.KY), dp, N.ptr(self.rowsum), self.splits,
+               N.ptr(self.KY), ldy, self.splits_fb, N.ptr(self.Y), ldy, self.row0, self.m, self.d,
+               dp, self.state.ptr, guard, float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx,
+               s)
 
     # ---------------------------------------------------- pair split --
     @classmethod
@@ -852,6 +914,8 @@ class PhiEngine(object):
         None: not the h2 engine) -- synchronises."""
         if self.phi_gemm != "h2" or self.d <= self.DIRECT_MAX_D:
             return None
+        if self.phi_form == "w":
+            return bool(float(self.wscale[2 * self.dp + 2]) != 0.0)
         return bool(float(self.yscale[2 * self.ldy + 2]) != 0.0)
 
     # --------------------------------------------------------------- KSD --
@@ -873,6 +937,8 @@ class PhiEngine(object):
         layout (no pair split)."""
         if self.plan is not None:
             raise ValueError("ksd() does not support the pair-split layout")
+        if self.phi_form == "w":
+            raise ValueError("ksd() needs K . Xc: build the engine with phi_form='xs' (the default)")
         if self.score_scale != 1.0:
             raise ValueError("ksd() needs the scores packed with score_scale == 1.0 (got %r)"
                              % (self.score_scale,))

@@ -73,7 +73,10 @@ class Sampler(object):
         hist = torch.empty(num_iter + 1, n, d, dtype=torch.float32, device=dev)
         S = torch.empty(n, d, dtype=torch.float32, device=dev)
         median = self._rbf.median
-        engine = PhiEngine(n, d, device=dev) if (order == "jacobi" or median) else None
+        # (ksd() reads K . Xc, which only the two-operand phi_mm leaves behind)
+        form = "w" if ksd_every is None else "xs"
+        engine = (PhiEngine(n, d, device=dev, phi_form=form)
+                  if (order == "jacobi" or median) else None)
         state = engine.state if engine is not None else SelectState(dev)
         if not median:
             N.call("dsvgd_set_bandwidth", state.ptr, float(self._rbf.h), N.stream(dev))

@@ -588,6 +588,57 @@ int dsvgd_phi_finish(const float* KY, int64_t ldk, const float* rowsum, int64_t 
  * thread.  Same bits.  Returns the previous setting. */
 int dsvgd_phi_set_finish_vec(int on);
 
+/* ---- phi_mm in the ONE-OPERAND form ---------------------------------------
+ * K S - (2/h) K Xc = K W with W = S - (2/h) Xc, so
+ *   phi_i = inv_n (s_i + (K W)_i + (2/h) r_i xc_i)
+ * needs one dp-wide product instead of K [Xc | S] (2 dp wide): half the
+ * MFMAs, half the B image and half the split-K partials, for the same staging
+ * of K.  The form is a property of the caller (an engine picks it once); the
+ * two-operand entry points above are unchanged.  Requires the fused scales
+ * (dsvgd_pack_h2's maxima, ldy <= dsvgd_pack_max_ldy()) and dp % 256 == 0.
+ *
+ * dsvgd_h2_wscales (after the bandwidth is in `st`; t = 2 st->inv_h): the
+ * power-of-two column scales of W in dsvgd_h2_colscale's layout over dp
+ * columns (wscale: 2 dp + 3 floats), from the bound b_c = max|S_c| + t
+ * max|Xc_c| (s_c b_c in [2^14, 2^15); at most one bit of the 22 lost), and
+ * the RANGE GUARD wscale[2 dp + 2], at least as conservative as
+ * dsvgd_h2_scales over all of Y: 1.0 when that guard fires (a half of Y
+ * spans more than 2^16 between its largest magnitude and its smallest
+ * nonzero row max), or when max(gS, t gX) > 2^16 min(rS, t rX) (g: a half's
+ * largest magnitude, r: its smallest nonzero row max), else 0.0.
+ * dsvgd_h2_wsplit: Wh[kstep][part][column][16] (dsvgd_h2_image_bytes(rows,
+ * dp) bytes) of wscale[c] * fmaf(-t, Y[r][c], Y[r][dp + c]) -- dsvgd_h2_ysplit's
+ * image over dp columns; Y's zero padding gives zero rows >= n, columns >= d.
+ * dsvgd_phi_mm_h2w: dsvgd_phi_mm_h2's arguments with the W image, ldw = dp
+ * (a multiple of 256) and colinv = &wscale[dp]; partials KW[splits][m][ldk]
+ * (ldk >= dp) and the row sums as dsvgd_phi_mm_h2; the full layout with any
+ * row block, or sym = 1 (m == n, row0 == 0) in one launch.  gate =
+ * &wscale[2 dp + 2]: does nothing while it reads nonzero -- the caller runs
+ * the two-operand FmtX3 fallback (dsvgd_ysplit + dsvgd_phi_mm_x3, or
+ * dsvgd_phi_mm_gated) behind it on the same word.
+ * dsvgd_phi_splits_w: the slice count (every fp32 chain within 16384
+ * columns, at least two rounds of blocks per CU; m = n = 65536, dp = 256: 4).
+ * dsvgd_phi_finish_w: dsvgd_phi_finish for this form.  *guard == 0: sums the
+ * `splits` slices of KW (row stride ldk) and forms the phi above; nonzero:
+ * dsvgd_phi_finish's formula, in its order, on the `splits_fb` two-operand
+ * slices the fallback left in KY (row stride ldky >= 2 dp).  KW and KY may be
+ * one buffer.  extra, phi, X as dsvgd_phi_finish. */
+int dsvgd_h2_wscales(const uint32_t* partial, const uint32_t* gmax, int64_t nb, int64_t ldy,
+                     int64_t dp, const dsvgd_select_state* st, float* wscale, void* stream);
+int dsvgd_h2_wsplit(const float* Y, int64_t ldy, int64_t rows, int64_t dp,
+                    const dsvgd_select_state* st, const float* wscale, void* Wh, void* stream);
+int64_t dsvgd_phi_splits_w(int64_t m, int64_t n, int64_t dp);
+int dsvgd_phi_mm_h2w(const float* D, int64_t ldd, const void* Wh, int64_t ldw, int64_t row0,
+                     int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KW,
+                     int64_t ldk, float* rowsum, int sym, const float* colinv, const float* gate,
+                     void* stream);
+int dsvgd_phi_finish_w(const float* KW, int64_t ldk, const float* rowsum, int64_t splits,
+                       const float* KY, int64_t ldky, int64_t splits_fb, const float* Y,
+                       int64_t ldy, int64_t row0, int64_t m, int64_t d, int64_t dp,
+                       const dsvgd_select_state* st, const float* guard, float inv_n, float step,
+                       const float* extra, int64_t lde, float* phi, int64_t ldphi, float* X,
+                       int64_t ldx, void* stream);
+
 /* d <= 64 (used for d <= 2): phi (and the optional X update) straight from the pairwise form
  * phi_i = inv_n sum_j k_ij (s_j + (2/h)(x_i - x_j)) on the VALU -- the
  * reference's own per-pair expression (dsvgd/sampler.py:38-40), which avoids
