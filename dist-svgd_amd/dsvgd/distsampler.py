@@ -82,6 +82,7 @@ Deviation: exchange_scores with num_shards == 1 uses the local scores (the
 reference reads an uninitialised buffer there).
 """
 import warnings
+import weakref
 
 import torch
 
@@ -182,6 +183,7 @@ class DistSampler(object):
         self._sbuf = None
         self._graph = None
         self._graph_key = None
+        self._sweep_hold = {}    # the sequential sweep's workspace (_graph points into it)
         self._group_checked = False
         self._warn_w2_cost()
 
@@ -448,6 +450,11 @@ class DistSampler(object):
         ps = self._use_pair_split(n_int, m) and self._pair_split_routes(m)
         key = (n_int, m, local, ps)
         if key not in self._engines:
+            if self._engines:
+                # a captured step points into the engine that goes (the key
+                # is fixed at S = 1, where steps are captured; kept safe
+                # should that change): capture again on the new one
+                self._graph = None
             self._engines.clear()      # the old D is freed before the new one is allocated
             self._engines[key] = PhiEngine(
                 n_int, self._d, m=m, row0=row0, device=self._device, local_median=local,
@@ -565,7 +572,7 @@ class DistSampler(object):
                        N.stream(self._device))
             tgt = None if self._exchange_scores else self._target
             sequential_sweep(Xi, Si, range(us - lo, ue - lo), state, step_size, target=tgt,
-                             score_scale=scale, extra=w2g)
+                             score_scale=scale, extra=w2g, hold=self._sweep_hold)
 
 
     def make_step(self, step_size, h=1.0):
@@ -601,7 +608,11 @@ class DistSampler(object):
                 and isinstance(self._target, BuiltinTarget)):
             key = float(step_size)
             if self._graph is None or self._graph_key != key:
-                self._graph = StepGraph(lambda: self._compute(step_size, h), self._device)
+                # (a weak reference: sampler -> graph -> closure -> sampler would
+                # be a cycle, and the sampler's D, graph and streams would wait
+                # for the cyclic collector instead of going with the sampler)
+                me = weakref.proxy(self)
+                self._graph = StepGraph(lambda: me._compute(step_size, h), self._device)
                 self._graph_key = key
             self._graph()
         else:

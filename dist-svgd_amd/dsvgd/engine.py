@@ -16,7 +16,9 @@ The hist all-reduce hook is where a DistSampler with a row-sharded D makes the
 median global (RCCL all_reduce of 2048 int64 counts per pass).
 """
 import ctypes
+import gc
 import math
+import weakref
 
 import torch
 
@@ -1065,8 +1067,21 @@ class StepGraph(object):
         if self.graph is None:
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.device(self.device), torch.cuda.graph(g):
-                self.fn()
+            # No cyclic collection inside the capture: a dead cycle may hold
+            # device resources (another sampler's graph and its pool, streams,
+            # tensors), and their destructors make calls that a capturing
+            # stream does not permit -- the process aborts.  torch.cuda.graph
+            # no longer collects on entry, so collect here and hold the
+            # collector off until the capture has ended.
+            gc.collect()
+            was_enabled = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.device(self.device), torch.cuda.graph(g):
+                    self.fn()
+            finally:
+                if was_enabled:
+                    gc.enable()
             self.graph = g
         self.graph.replay()
 
@@ -1095,7 +1110,7 @@ def _gs_score_kind(target):
 
 
 def sequential_sweep(X, S, rows, h_state, step, target=None, score_scale=1.0, phi_out=None,
-                     extra=None, blocked=True):
+                     extra=None, blocked=True, hold=None):
     """Gauss-Seidel sweep in the reference order over `rows` of the interacting
     set X (n, d): for each i, phi_i from the CURRENT X (earlier rows already
     moved), X[i] += step * (phi_i + extra[k]), then (if `target`) S[i] is
@@ -1109,7 +1124,12 @@ def sequential_sweep(X, S, rows, h_state, step, target=None, score_scale=1.0, ph
     d <= 64 with an elementwise target on the VALU form, 64 < d <= 1024 (and
     the logistic regression at any d <= 1024, its score refreshed in the
     walk) on the wide one; otherwise one row kernel (+ one score refresh) per
-    row."""
+    row.
+
+    hold: a dict the caller owns.  The wide sweep's workspace is stored in it,
+    so it lives as long as the dict does: a caller that captures the sweep in
+    a StepGraph keeps `hold` beside the graph, whose kernels hold raw pointers
+    into the workspace (the module's cache alone holds it weakly)."""
     n, d = X.shape
     s = N.stream(X.device)
     if extra is not None:
@@ -1124,7 +1144,7 @@ def sequential_sweep(X, S, rows, h_state, step, target=None, score_scale=1.0, ph
             return
         if d <= GSW_MAX_D:
             _blocked_sweep_wide(X, S, rows, h_state, step, kind, target, score_scale, phi_out,
-                                extra, s)
+                                extra, s, hold)
             return
     blocks = int(N.load().dsvgd_phi_row_blocks(n, d))
     part = None
@@ -1236,7 +1256,13 @@ class _WideSweep(object):
                    0 if self.m16 else 1, None, s)
 
 
-_WIDE = {}
+# key -> _WideSweep, held weakly: a workspace lives while an owner holds it
+# (sequential_sweep's `hold`: the samplers, for as long as their captured
+# graphs point into it) or while it is the last one used (_WIDE_LAST), so a
+# sweep of another shape frees the old D before it allocates its own only
+# when nobody replays through it any more
+_WIDE = weakref.WeakValueDictionary()
+_WIDE_LAST = []
 # the pipelined wide sweep (round 6): group g + 1's wide pass on a second
 # stream while group g walks, group g's columns left out of it and added at
 # their moved positions by dsvgd_gsw_group_corr before g + 1 walks
@@ -1258,7 +1284,8 @@ GSW_GROUP = None
 GSW_SPLITS = None
 
 
-def _blocked_sweep_wide(X, S, rows, h_state, step, kind, target, score_scale, phi_out, extra, s):
+def _blocked_sweep_wide(X, S, rows, h_state, step, kind, target, score_scale, phi_out, extra, s,
+                        hold=None):
     """The reference's Gauss-Seidel sweep for 64 < d <= 1024, B rows at a
     time: the block's interactions with every row not moved before it in the
     block on the MFMA engines (the Gram, dsvgd_gs_mask, phi_mm over split-K
@@ -1269,8 +1296,11 @@ def _blocked_sweep_wide(X, S, rows, h_state, step, kind, target, score_scale, ph
     key = (X.device, n, d, GSW_GEMM, kind != 0, GSW_GROUP, GSW_SPLITS)
     W = _WIDE.get(key)
     if W is None:
-        _WIDE.clear()
+        del _WIDE_LAST[:]     # the old D is freed before the new one is allocated
         W = _WIDE[key] = _WideSweep(X.device, n, d, GSW_GEMM, kind)
+    _WIDE_LAST[:] = [W]
+    if hold is not None and hold.get("wide") is not W:
+        hold["wide"] = W
     sk, mu, lam, xd, td = kind, None, None, None, None
     if sk == 1:
         mu, lam = target._params(X.device)

@@ -81,6 +81,7 @@ class Sampler(object):
         if not median:
             N.call("dsvgd_set_bandwidth", state.ptr, float(self._rbf.h), N.stream(dev))
         target = self._target
+        hold = {}    # the sweep's workspace, alive while `step` replays through it
 
         def iteration():
             target.score(X, S)
@@ -92,7 +93,7 @@ class Sampler(object):
                     engine.pack(X)
                     engine.distances(median=True)
                     engine.median_bandwidth()
-                sequential_sweep(X, S, range(n), state, step_size, target=target)
+                sequential_sweep(X, S, range(n), state, step_size, target=target, hold=hold)
 
         # built-in targets are pure kernel launches: capture the iteration
         # once and replay it (user callables run eagerly)
