@@ -60,6 +60,16 @@ __device__ __forceinline__ float pow2_inv(float s) {
   return __uint_as_float(0x7F000000u - __float_as_uint(s));
 }
 
+// Kernel families of the fused A staging (include/dsvgd.h DSVGD_KERNEL_*): a
+// template parameter of every staging site, so the RBF instantiations keep
+// their code.  The IMQ powers of u = 1 + D/h in one form,
+//   u^e 2^off = exp2(e log2(fma(D, 1/h, 1)) + off),   e < 0:
+// the +inf pads of D give log2 = +inf and exp2(-inf) = 0, as exp(-inf) does.
+constexpr int kFamRBF = DSVGD_KERNEL_RBF, kFamIMQ = DSVGD_KERNEL_IMQ;
+__device__ __forceinline__ float imq_pow(float v, float inv_h, float e, float off) {
+  return __builtin_amdgcn_exp2f(fmaf(e, __builtin_amdgcn_logf(fmaf(v, inv_h, 1.f)), off));
+}
+
 __device__ __forceinline__ float warp_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -214,7 +214,8 @@ struct NTTile {
 // 2 x (16 KiB A + 64 KiB B) = 160 KiB, so the A image drops its row padding
 // and XOR-swizzles its 16-B chunks instead: chunk' = chunk ^ ((row >> 1) & 7)
 // keeps a ds_read_b128 lane group (16 rows, 2 per 64-bank line) conflict-free.
-template <int TN, bool EXP, int WM = 2, int TM_ = 4 / WM, int BJ_ = 16, bool SWZB = true>
+template <int TN, bool EXP, int WM = 2, int TM_ = 4 / WM, int BJ_ = 16, bool SWZB = true,
+          int FAM = kFamRBF>
 struct NNTile {
   static constexpr int kThreads = 256 * WM;
   static constexpr int TM = TM_;
@@ -238,6 +239,15 @@ struct NNTile {
   f32x16 acc[TM][TN];
   f32x4 ra[LA], rb[LB];
   float rs[RPT];  // EXP: row-sum partials of the rows this thread stages
+  float pw;       // FAM = IMQ: the exponent e of u^e (`scale` is then 1/h)
+
+  // the staged kernel value of one D entry
+  __device__ __forceinline__ float kval(float v, float scale) const {
+    if constexpr (FAM == kFamIMQ)
+      return imq_pow(v, scale, pw, 0.f);
+    else
+      return __builtin_amdgcn_exp2f(v * scale);
+  }
 
   // A image offset of (row, 16-B chunk)
   __device__ __forceinline__ static int a_off(int row, int chunk) {
@@ -311,10 +321,10 @@ struct NNTile {
           const int qd = (int)dgl + row - 4 * chunk;
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            ra[u][q] = (qd == q) ? 0.f : __builtin_amdgcn_exp2f(ra[u][q] * scale);
+            ra[u][q] = (qd == q) ? 0.f : kval(ra[u][q], scale);
         } else {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) ra[u][q] = __builtin_amdgcn_exp2f(ra[u][q] * scale);
+          for (int q = 0; q < 4; ++q) ra[u][q] = kval(ra[u][q], scale);
         }
         rs[u % RPT] += (ra[u][0] + ra[u][1]) + (ra[u][2] + ra[u][3]);
       }

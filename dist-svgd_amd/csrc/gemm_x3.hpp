@@ -174,7 +174,7 @@ __device__ __forceinline__ int x3_off(int x, int h) { return x * 32 + ((h ^ ((x 
 // ping-pong staging order, DMA issue after the first MFMA half, branch-free
 // staging interleaved by sched_group_barrier.)
 template <int TN, bool DMA = true, bool EXP = true, bool M16 = false, int RW = 2, class F = FmtX3,
-          int NB = 2>
+          int NB = 2, int FAM = kFamRBF>
 struct NNX3Tile {
   static constexpr int P = F::P;
   static_assert(NB == 2 || (NB == 3 && DMA), "3-stage ring: DMA path");
@@ -207,7 +207,16 @@ struct NNX3Tile {
   int64_t prow = 0;  // RW = 4: bytes between the block's two D panel rows
   u32x4 rb[DMA ? 1 : LB];
   float rs;
+  float pw;      // FAM = IMQ: the exponent e of u^e (`scale` is then 1/h)
   V8 a[TM][P];
+
+  // the staged kernel value of one D entry, with the format's A scale
+  __device__ __forceinline__ float kval(float v, float scale) const {
+    if constexpr (FAM == kFamIMQ)
+      return imq_pow(v, scale, pw, F::kAScaleLog2);
+    else
+      return __builtin_amdgcn_exp2f(fmaf(v, scale, F::kAScaleLog2));
+  }
 
   // A: thread t stages row t >> 2, columns 4 (t & 3) .. +3 of the D panel.
   // B: 16-B chunk f = t + 512 u of the block's K-step image (part f / (2 BC)).
@@ -258,10 +267,10 @@ struct NNX3Tile {
       const int qd = (int)dgl + row - 4 * c4;
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        ra[q] = (qd == q) ? 0.f : __builtin_amdgcn_exp2f(fmaf(ra[q], scale, F::kAScaleLog2));
+        ra[q] = (qd == q) ? 0.f : kval(ra[q], scale);
     } else {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) ra[q] = __builtin_amdgcn_exp2f(fmaf(ra[q], scale, F::kAScaleLog2));
+      for (int q = 0; q < 4; ++q) ra[q] = kval(ra[q], scale);
     }
     if (EXP) rs += (ra[0] + ra[1]) + (ra[2] + ra[3]);
     typename F::V4 sp[P];

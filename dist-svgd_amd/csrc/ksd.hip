@@ -9,6 +9,14 @@
 //   a_j = s_j.xc_j,  b_i = sum_{j != i} k_ij a_j,  q_i = sum_{j != i} k_ij D_ij.
 // KXc, KS, r are phi_mm's outputs; b and q are the one sweep over D below.
 //
+// For the inverse multiquadric k = u^beta, u = 1 + D/h (FAM = IMQ below), with
+// F = u^beta, G' = u^(beta-1), H' = u^(beta-2), c1 = -2 beta/h, c2 = 4 beta
+// (beta-1)/h^2:
+//   u_ij = F s_i.s_j + c1 G' [(s_i - s_j).(x_i - x_j) + d] - c2 H' D_ij,
+//   t_i = s_i.FS_i + c1 [rG_i a_i - s_i.G'Xc_i - xc_i.G'S_i + b_i + d rG_i] - c2 q_i,
+//   b_i = sum_{j != i} G'_ij a_j,  q_i = sum_{j != i} H'_ij D_ij,  u_ii = |s_i|^2 + c1 d.
+// FS comes from phi_mm's F run, G'Xc, G'S and rG from its G' run.
+//
 // Everything is deterministic: no float atomics, every partial has a slot of
 // its own and every sum a fixed order.
 #include <algorithm>
@@ -51,16 +59,29 @@ __global__ __launch_bounds__(256) void ksd_a_kernel(const float* __restrict__ Y,
 // per column, cv[4..7] = their k a_i (the transposed tile's terms).  MASK:
 // entries with a row or column past the matrix (+inf pads: exp(-inf) inf is
 // NaN) or on the diagonal contribute exactly 0.
-template <bool MASK, bool COLS>
+// FAM = IMQ: k -> G' = u^pw (pw = beta - 1, scale = 1/h) and k D -> H' D =
+// u^(pw-1) D.
+template <bool MASK, bool COLS, int FAM = kFamRBF>
 __device__ __forceinline__ void ksd_panel(const f32x4 v0, const f32x4 v1, const f32x4 a4,
                                           float scale, int64_t g0, int64_t j0, bool rv0, bool rv1,
                                           int64_t n, float ai0, float ai1, float& q0, float& b0,
-                                          float& q1, float& b1, float* cv) {
+                                          float& q1, float& b1, float* cv, float pw = 0.f) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    float k0 = __builtin_amdgcn_exp2f(v0[e] * scale);
-    float k1 = __builtin_amdgcn_exp2f(v1[e] * scale);
-    float kd0 = k0 * v0[e], kd1 = k1 * v1[e];
+    float k0, k1, kd0, kd1;
+    if constexpr (FAM == kFamIMQ) {
+      const float l0 = __builtin_amdgcn_logf(fmaf(v0[e], scale, 1.f));
+      const float l1 = __builtin_amdgcn_logf(fmaf(v1[e], scale, 1.f));
+      k0 = __builtin_amdgcn_exp2f(pw * l0);
+      k1 = __builtin_amdgcn_exp2f(pw * l1);
+      kd0 = __builtin_amdgcn_exp2f((pw - 1.f) * l0) * v0[e];
+      kd1 = __builtin_amdgcn_exp2f((pw - 1.f) * l1) * v1[e];
+    } else {
+      k0 = __builtin_amdgcn_exp2f(v0[e] * scale);
+      k1 = __builtin_amdgcn_exp2f(v1[e] * scale);
+      kd0 = k0 * v0[e];
+      kd1 = k1 * v1[e];
+    }
     if (MASK) {
       const int64_t j = j0 + e;
       const bool ok0 = rv0 && j < n && j != g0;
@@ -92,16 +113,17 @@ __device__ __forceinline__ float quad_sum(float v) {
 // I in column slice z; thread t reads two 16-byte pieces per panel (rows t/4
 // and t/4 + 64, columns 4 (t % 4) ..), a wave 1 KiB contiguous per load.
 // P[z][0][i] = q, P[z][1][i] = b of the slice.  No LDS.
+template <int FAM = kFamRBF>
 __global__ __launch_bounds__(256) void ksd_rows_full_kernel(
     const float* __restrict__ D, int64_t n_pad, const float* __restrict__ a, int64_t row0,
     int64_t m, int64_t n, const dsvgd_select_state* __restrict__ st, int parts,
-    float* __restrict__ P, int64_t m_pad) {
+    float* __restrict__ P, int64_t m_pad, float pw = 0.f) {
   const int t = threadIdx.x, cq = t & 3, r0 = t >> 2;
   const int64_t I = blockIdx.x;
   const int z = blockIdx.y;
   const int64_t pcols = n_pad >> 4;
   const int64_t c0 = pcols * z / parts, c1 = pcols * (z + 1) / parts;
-  const float scale = -st->inv_h * kLog2e;
+  const float scale = FAM == kFamIMQ ? st->inv_h : -st->inv_h * kLog2e;
   const int64_t i0 = I * 128 + r0;
   const bool rv0 = i0 < m, rv1 = i0 + 64 < m;
   const int64_t g0 = row0 + i0;          // the row's own column
@@ -117,11 +139,11 @@ __global__ __launch_bounds__(256) void ksd_rows_full_kernel(
     const int64_t j0 = 16 * c + 4 * cq;
     const bool edge = row_edge || 16 * c + 16 > n || (16 * c + 15 >= gt && 16 * c <= gt + 127);
     if (edge)
-      ksd_panel<true, false>(v0, v1, a4, scale, g0, j0, rv0, rv1, n, 0.f, 0.f, q0, b0, q1, b1,
-                             nullptr);
+      ksd_panel<true, false, FAM>(v0, v1, a4, scale, g0, j0, rv0, rv1, n, 0.f, 0.f, q0, b0, q1, b1,
+                                  nullptr, pw);
     else
-      ksd_panel<false, false>(v0, v1, a4, scale, g0, j0, rv0, rv1, n, 0.f, 0.f, q0, b0, q1, b1,
-                              nullptr);
+      ksd_panel<false, false, FAM>(v0, v1, a4, scale, g0, j0, rv0, rv1, n, 0.f, 0.f, q0, b0, q1,
+                                   b1, nullptr, pw);
   }
   q0 = quad_sum(q0);
   q1 = quad_sum(q1);
@@ -186,16 +208,17 @@ __device__ __forceinline__ float ksd_col_reduce(const float* v, int lane) {
 // weights a_i, i in I) go to slot rparts + I at rows of J -- one slot per
 // stored tile row, summed by the finish for I < J in order.  The diagonal
 // tile counts once, without its diagonal.
+template <int FAM = kFamRBF>
 __global__ __launch_bounds__(256) void ksd_rows_sym_kernel(
     const float* __restrict__ D, int64_t n_pad, const float* __restrict__ a, int64_t n,
-    const dsvgd_select_state* __restrict__ st, int rparts, float* __restrict__ P) {
+    const dsvgd_select_state* __restrict__ st, int rparts, float* __restrict__ P, float pw = 0.f) {
   __shared__ float red[4][2][128];
   const int t = threadIdx.x, cq = t & 3, r0 = t >> 2, lane = t & 63, wv = t >> 6;
   const int64_t I = blockIdx.x;
   const int z = blockIdx.y;
   const int64_t T = n_pad >> 7, pcols = n_pad >> 4, len = T - I;
   const int64_t J0 = I + len * z / rparts, J1 = I + len * (z + 1) / rparts;
-  const float scale = -st->inv_h * kLog2e;
+  const float scale = FAM == kFamIMQ ? st->inv_h : -st->inv_h * kLog2e;
   const int64_t i0 = I * 128 + r0;
   const bool rv0 = i0 < n, rv1 = i0 + 64 < n;
   const float ai0 = a[i0], ai1 = a[i0 + 64];
@@ -218,11 +241,11 @@ __global__ __launch_bounds__(256) void ksd_rows_sym_kernel(
       const int64_t j0 = 16 * c + 4 * cq;
       float cv[8];
       if (edge)
-        ksd_panel<true, true>(v0, v1, a4, scale, i0, j0, rv0, rv1, n, ai0, ai1, q0, b0, q1, b1,
-                              cv);
+        ksd_panel<true, true, FAM>(v0, v1, a4, scale, i0, j0, rv0, rv1, n, ai0, ai1, q0, b0, q1, b1,
+                                   cv, pw);
       else
-        ksd_panel<false, true>(v0, v1, a4, scale, i0, j0, rv0, rv1, n, ai0, ai1, q0, b0, q1, b1,
-                               cv);
+        ksd_panel<false, true, FAM>(v0, v1, a4, scale, i0, j0, rv0, rv1, n, ai0, ai1, q0, b0, q1,
+                                    b1, cv, pw);
       if (!diag) {  // block-uniform
         const float y = ksd_col_reduce(cv, lane);
         if (lane < 32) red[wv][cqty][16 * p + ccol] = y;
@@ -254,11 +277,34 @@ __global__ __launch_bounds__(256) void ksd_rows_sym_kernel(
 // sums are added in order.  Then one wave per row: the split-K slices summed
 // in slice order in fp32 as phi_finish does, the five dot products in fp64.
 // ws[2 blk], ws[2 blk + 1] = the workgroup's sums of t and u_ii in row order.
+// FAM = IMQ: KY is the F run's [F Xc | F S], KG the G' run's [G' Xc | G' S]
+// (row stride ldkg, the same slices), rowsum the G' run's rG.  KG, ldkg and
+// beta arrive as one trailing KsdImqArgs that only the IMQ instantiation has
+// (KA is empty for the RBF, whose argument block and code stay what they were).
+struct KsdImqArgs {
+  const float* KG;
+  int64_t ldkg;
+  float beta;
+};
+template <class... KA>
+__device__ __forceinline__ KsdImqArgs ksd_imq_args(KA... ka) {
+  if constexpr (sizeof...(KA) == 0)
+    return KsdImqArgs{nullptr, 0, 0.f};
+  else
+    return (ka, ...);
+}
+
+template <int FAM = kFamRBF, class... KA>
 __global__ __launch_bounds__(256) void ksd_finish_kernel(
     const float* __restrict__ KY, int64_t ldk, const float* __restrict__ rowsum, int splits,
     const float* __restrict__ Y, int64_t ldy, int64_t dp, int64_t d, int64_t row0, int64_t m,
     int64_t m_pad, const dsvgd_select_state* __restrict__ st, int sym, int parts,
-    const float* __restrict__ P, float* __restrict__ rows, double* __restrict__ ws) {
+    const float* __restrict__ P, float* __restrict__ rows, double* __restrict__ ws, KA... ka) {
+  static_assert(sizeof...(KA) == (FAM == kFamIMQ ? 1 : 0), "KsdImqArgs: the IMQ instantiation only");
+  [[maybe_unused]] const KsdImqArgs ia = ksd_imq_args(ka...);
+  [[maybe_unused]] const float* const KG = ia.KG;
+  [[maybe_unused]] const int64_t ldkg = ia.ldkg;
+  [[maybe_unused]] const float beta = ia.beta;
   __shared__ double shq[4][64], shb[4][64], sht[4][2];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int64_t ib = (int64_t)blockIdx.x * kKsdRowsPerBlock;
@@ -280,7 +326,8 @@ __global__ __launch_bounds__(256) void ksd_finish_kernel(
     shb[wv][lane] = b;
   }
   __syncthreads();
-  const double ih = (double)st->inv_h, g = 2.0 * ih;
+  // RBF: g = 2/h (and g^2 = 4/h^2 below); IMQ: c1 (and c2) in their places
+  const double ih = (double)st->inv_h, g = FAM == kFamIMQ ? -2.0 * (double)beta * ih : 2.0 * ih;
   double wt = 0.0, wu = 0.0;
   for (int k = 0; k < 16; ++k) {
     const int rr = 16 * wv + k;
@@ -289,16 +336,25 @@ __global__ __launch_bounds__(256) void ksd_finish_kernel(
     const float* yi = Y + (row0 + i) * ldy;
     double sKS = 0.0, sKX = 0.0, xKS = 0.0, aa = 0.0, ss = 0.0;
     for (int64_t c = lane; c < d; c += 64) {
-      float kx = 0.f, ks = 0.f;
+      float kx = 0.f, ks = 0.f, gs = 0.f;
       for (int zz = 0; zz < splits; ++zz) {
         const float* ky = KY + ((int64_t)zz * m + i) * ldk;
-        kx += ky[c];
+        if constexpr (FAM == kFamIMQ) {
+          const float* kg = KG + ((int64_t)zz * m + i) * ldkg;
+          kx += kg[c];
+          gs += kg[dp + c];
+        } else {
+          kx += ky[c];
+        }
         ks += ky[dp + c];
       }
       const double x = (double)yi[c], s = (double)yi[dp + c];
       sKS += s * (double)ks;
       sKX += s * (double)kx;
-      xKS += x * (double)ks;
+      if constexpr (FAM == kFamIMQ)
+        xKS += x * (double)gs;
+      else
+        xKS += x * (double)ks;
       aa += s * x;
       ss += s * s;
     }
@@ -312,7 +368,12 @@ __global__ __launch_bounds__(256) void ksd_finish_kernel(
     const double q = ((shq[0][rr] + shq[1][rr]) + shq[2][rr]) + shq[3][rr];
     const double b = ((shb[0][rr] + shb[1][rr]) + shb[2][rr]) + shb[3][rr];
     const double rd = (double)r, dd = (double)d;
-    const double ti = sKS + g * (rd * aa - sKX - xKS + b) + g * dd * rd - g * g * q;
+    double ti;
+    if constexpr (FAM == kFamIMQ)
+      ti = sKS + g * (rd * aa - sKX - xKS + b) + g * dd * rd -
+           4.0 * (double)beta * ((double)beta - 1.0) * ih * ih * q;
+    else
+      ti = sKS + g * (rd * aa - sKX - xKS + b) + g * dd * rd - g * g * q;
     const double ui = ss + g * dd;
     if (lane == 0 && rows) rows[i] = (float)ti;
     wt += ti;
@@ -359,10 +420,11 @@ __global__ __launch_bounds__(256) void ksd_reduce_kernel(const double* __restric
 // d <= 64: t_i from explicit differences, straight from Y.  Workgroup: 64
 // rows; thread (r, g) takes row r and the columns jj = g mod 4 of each staged
 // chunk; the four partial sums of a row are added in g order.
+template <int FAM = kFamRBF>
 __global__ __launch_bounds__(256) void ksd_direct_kernel(
     const float* __restrict__ Y, int64_t ldy, int64_t dp, int d, int64_t row0, int64_t m,
     int64_t n, const dsvgd_select_state* __restrict__ st, float* __restrict__ rows,
-    double* __restrict__ ws) {
+    double* __restrict__ ws, float beta = 0.f) {
   __shared__ float xi[kKsdDirectMaxD * 64], si[kKsdDirectMaxD * 64];            // [c][r]
   __shared__ float xj[kKsdDirectJ * kKsdDirectMaxD], sj[kKsdDirectJ * kKsdDirectMaxD];  // [jj][c]
   __shared__ double part[4][64];
@@ -377,7 +439,10 @@ __global__ __launch_bounds__(256) void ksd_direct_kernel(
   }
   const float ihf = st->inv_h;
   const float scale = -ihf * kLog2e;
-  const double gg = 2.0 * (double)ihf, cst = gg * (double)d;
+  // RBF: gg = 2/h; IMQ: c1, and c2 where the RBF has gg^2
+  const double gg = FAM == kFamIMQ ? -2.0 * (double)beta * (double)ihf : 2.0 * (double)ihf;
+  const double cst = gg * (double)d;
+  const double c2 = 4.0 * (double)beta * ((double)beta - 1.0) * (double)ihf * (double)ihf;
   double acc = 0.0;
   for (int64_t j0 = 0; j0 < n; j0 += kKsdDirectJ) {
     __syncthreads();
@@ -401,8 +466,18 @@ __global__ __launch_bounds__(256) void ksd_direct_kernel(
         ssum = fmaf(s, so, ssum);
         sd = fmaf(s - so, dx, sd);
       }
-      const float k = __builtin_amdgcn_exp2f(Dij * scale);
-      const double u = (double)k * ((double)ssum + gg * (double)sd + cst - gg * gg * (double)Dij);
+      double u;
+      if constexpr (FAM == kFamIMQ) {
+        const float lg = __builtin_amdgcn_logf(fmaf(Dij, ihf, 1.f));
+        const float f = __builtin_amdgcn_exp2f(beta * lg);
+        const float gp = __builtin_amdgcn_exp2f((beta - 1.f) * lg);
+        const float hp = __builtin_amdgcn_exp2f((beta - 2.f) * lg);
+        u = (double)f * (double)ssum + (double)gp * (gg * (double)sd + cst) -
+            c2 * (double)hp * (double)Dij;
+      } else {
+        const float k = __builtin_amdgcn_exp2f(Dij * scale);
+        u = (double)k * ((double)ssum + gg * (double)sd + cst - gg * gg * (double)Dij);
+      }
       if (j != row0 + i) acc += u;
     }
   }
@@ -428,6 +503,12 @@ static int64_t ksd_row_parts(int64_t tiles, int64_t cap) {
 }
 
 static bool a16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+
+static bool kern_ok(dsvgd_kernel k) {
+  return k.family == DSVGD_KERNEL_RBF ||
+         (k.family == DSVGD_KERNEL_IMQ && k.beta >= -1.f && k.beta < 0.f);
+}
+static const dsvgd_kernel kRbfKern = {DSVGD_KERNEL_RBF, 0.f};
 
 }  // namespace dsvgd
 
@@ -464,6 +545,17 @@ int dsvgd_ksd_gate(const float* rowsum, int64_t splits, int64_t m, int64_t n, fl
 int dsvgd_ksd_rows(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t dp, int64_t d,
                    int64_t row0, int64_t m, int64_t n, const dsvgd_select_state* st, int sym,
                    int64_t parts, float* P, float* a, void* stream) {
+  return dsvgd_ksd_rows_kern(D, ldd, Y, ldy, dp, d, row0, m, n, st, sym, parts, P, a, kRbfKern,
+                             stream);
+}
+
+int dsvgd_ksd_rows_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t dp,
+                        int64_t d, int64_t row0, int64_t m, int64_t n,
+                        const dsvgd_select_state* st, int sym, int64_t parts, float* P, float* a,
+                        dsvgd_kernel kern, void* stream) {
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
+  const bool imq = kern.family == DSVGD_KERNEL_IMQ;
+  const float pw = kern.beta - 1.f;   // IMQ: the sweep's matrix is G' = u^(beta-1)
   DSVGD_REQUIRE(D && Y && st && P && a, "null pointer");
   DSVGD_REQUIRE(m > 0 && n > 0 && d > 0 && row0 >= 0 && row0 + m <= n, "sizes");
   const int64_t n_pad = roundup(n, 128), m_pad = roundup(m, 128);
@@ -479,12 +571,21 @@ int dsvgd_ksd_rows(const float* D, int64_t ldd, const float* Y, int64_t ldy, int
   if (rc) return rc;
   if (sym) {
     const int64_t T = n_pad / 128, rparts = parts - T;
-    hipLaunchKernelGGL(ksd_rows_sym_kernel, dim3((unsigned)T, (unsigned)rparts), dim3(256), 0, s, D,
-                       n_pad, a, n, st, (int)rparts, P);
+    if (imq)
+      hipLaunchKernelGGL(ksd_rows_sym_kernel<kFamIMQ>, dim3((unsigned)T, (unsigned)rparts),
+                         dim3(256), 0, s, D, n_pad, a, n, st, (int)rparts, P, pw);
+    else
+      hipLaunchKernelGGL(ksd_rows_sym_kernel<kFamRBF>, dim3((unsigned)T, (unsigned)rparts),
+                         dim3(256), 0, s, D, n_pad, a, n, st, (int)rparts, P, 0.f);
     return check_launch("ksd_rows_sym");
   }
-  hipLaunchKernelGGL(ksd_rows_full_kernel, dim3((unsigned)(m_pad / 128), (unsigned)parts),
-                     dim3(256), 0, s, D, n_pad, a, row0, m, n, st, (int)parts, P, m_pad);
+  const dim3 grid((unsigned)(m_pad / 128), (unsigned)parts);
+  if (imq)
+    hipLaunchKernelGGL(ksd_rows_full_kernel<kFamIMQ>, grid, dim3(256), 0, s, D, n_pad, a, row0, m,
+                       n, st, (int)parts, P, m_pad, pw);
+  else
+    hipLaunchKernelGGL(ksd_rows_full_kernel<kFamRBF>, grid, dim3(256), 0, s, D, n_pad, a, row0, m,
+                       n, st, (int)parts, P, m_pad, 0.f);
   return check_launch("ksd_rows_full");
 }
 
@@ -503,10 +604,38 @@ int dsvgd_ksd_finish(const float* KY, int64_t ldk, const float* rowsum, int64_t 
   const int64_t m_pad = roundup(m, 128);
   const int64_t nb = (m + kKsdRowsPerBlock - 1) / kKsdRowsPerBlock;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ksd_finish_kernel, dim3((unsigned)nb), dim3(256), 0, s, KY, ldk, rowsum,
-                     (int)splits, Y, ldy, dp, d, row0, m, m_pad, st, sym ? 1 : 0, (int)parts, P,
-                     rows, ws);
+  hipLaunchKernelGGL(ksd_finish_kernel<kFamRBF>, dim3((unsigned)nb), dim3(256), 0, s, KY, ldk,
+                     rowsum, (int)splits, Y, ldy, dp, d, row0, m, m_pad, st, sym ? 1 : 0,
+                     (int)parts, P, rows, ws);
   int rc = check_launch("ksd_finish");
+  if (rc) return rc;
+  hipLaunchKernelGGL(ksd_reduce_kernel, dim3(1), dim3(256), 0, s, ws, nb, n, out);
+  return check_launch("ksd_reduce");
+}
+
+int dsvgd_ksd_finish_imq(const float* KF, int64_t ldkf, const float* KG, int64_t ldkg,
+                         const float* rowsum, int64_t splits, const float* Y, int64_t ldy,
+                         int64_t dp, int64_t d, int64_t row0, int64_t m, int64_t n,
+                         const dsvgd_select_state* st, dsvgd_kernel kern, int sym, int64_t parts,
+                         const float* P, float* rows, double* ws, double* out, void* stream) {
+  DSVGD_REQUIRE(KF && KG && rowsum && Y && st && P && ws && out, "null pointer");
+  DSVGD_REQUIRE(kern.family == DSVGD_KERNEL_IMQ && kern_ok(kern),
+                "kern: the IMQ family with beta in [-1, 0)");
+  DSVGD_REQUIRE(m > 0 && n > 0 && d > 0 && row0 >= 0 && row0 + m <= n, "sizes");
+  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
+  DSVGD_REQUIRE(dp >= d && ldkf >= 2 * dp && ldkg >= 2 * dp && ldy >= 2 * dp,
+                "dp >= d, ldkf, ldkg, ldy >= 2 dp");
+  DSVGD_REQUIRE(!sym || (m == n && row0 == 0), "sym needs m == n and row0 == 0");
+  DSVGD_REQUIRE(parts == dsvgd_ksd_parts(m, n, sym), "parts must be dsvgd_ksd_parts(m, n, sym)");
+  DSVGD_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 7) == 0,
+                "ws and out must be 8-byte aligned");
+  const int64_t m_pad = roundup(m, 128);
+  const int64_t nb = (m + kKsdRowsPerBlock - 1) / kKsdRowsPerBlock;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ksd_finish_kernel<kFamIMQ>, dim3((unsigned)nb), dim3(256), 0, s, KF, ldkf,
+                     rowsum, (int)splits, Y, ldy, dp, d, row0, m, m_pad, st, sym ? 1 : 0,
+                     (int)parts, P, rows, ws, KsdImqArgs{KG, ldkg, kern.beta});
+  int rc = check_launch("ksd_finish(imq)");
   if (rc) return rc;
   hipLaunchKernelGGL(ksd_reduce_kernel, dim3(1), dim3(256), 0, s, ws, nb, n, out);
   return check_launch("ksd_reduce");
@@ -515,6 +644,13 @@ int dsvgd_ksd_finish(const float* KY, int64_t ldk, const float* rowsum, int64_t 
 int dsvgd_ksd_direct(const float* Y, int64_t ldy, int64_t dp, int64_t d, int64_t row0, int64_t m,
                      int64_t n, const dsvgd_select_state* st, float* rows, double* ws, double* out,
                      void* stream) {
+  return dsvgd_ksd_direct_kern(Y, ldy, dp, d, row0, m, n, st, rows, ws, out, kRbfKern, stream);
+}
+
+int dsvgd_ksd_direct_kern(const float* Y, int64_t ldy, int64_t dp, int64_t d, int64_t row0,
+                          int64_t m, int64_t n, const dsvgd_select_state* st, float* rows,
+                          double* ws, double* out, dsvgd_kernel kern, void* stream) {
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
   DSVGD_REQUIRE(Y && st && ws && out, "null pointer");
   DSVGD_REQUIRE(m > 0 && n > 0 && d > 0 && row0 >= 0 && row0 + m <= n, "sizes");
   DSVGD_REQUIRE(d <= kKsdDirectMaxD, "ksd_direct supports d <= 64");
@@ -523,8 +659,12 @@ int dsvgd_ksd_direct(const float* Y, int64_t ldy, int64_t dp, int64_t d, int64_t
                 "ws and out must be 8-byte aligned");
   const int64_t nb = (m + kKsdRowsPerBlock - 1) / kKsdRowsPerBlock;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ksd_direct_kernel, dim3((unsigned)nb), dim3(256), 0, s, Y, ldy, dp, (int)d,
-                     row0, m, n, st, rows, ws);
+  if (kern.family == DSVGD_KERNEL_IMQ)
+    hipLaunchKernelGGL(ksd_direct_kernel<kFamIMQ>, dim3((unsigned)nb), dim3(256), 0, s, Y, ldy, dp,
+                       (int)d, row0, m, n, st, rows, ws, kern.beta);
+  else
+    hipLaunchKernelGGL(ksd_direct_kernel<kFamRBF>, dim3((unsigned)nb), dim3(256), 0, s, Y, ldy, dp,
+                       (int)d, row0, m, n, st, rows, ws, 0.f);
   int rc = check_launch("ksd_direct");
   if (rc) return rc;
   hipLaunchKernelGGL(ksd_reduce_kernel, dim3(1), dim3(256), 0, s, ws, nb, n, out);

@@ -24,6 +24,16 @@ template <int DS, class... Args>
 static void launch_w1(dim3 grid, hipStream_t s, Args... args) {
   hipLaunchKernelGGL((phi_w1_kernel<DS>), grid, dim3(PhiW1::kThreads), 0, s, args...);
 }
+// the same with a kernel family: every argument spelled out, the IMQ
+// instantiations' exponent pw after them
+template <int DS, int FAM, class... Args>
+static void launch_w1k(dim3 grid, hipStream_t s, float pw, Args... args) {
+  if constexpr (FAM == kFamIMQ)
+    hipLaunchKernelGGL((phi_w1_kernel<DS, 4, true, FAM>), grid, dim3(PhiW1::kThreads), 0, s, args...,
+                       pw);
+  else
+    hipLaunchKernelGGL((phi_w1_kernel<DS>), grid, dim3(PhiW1::kThreads), 0, s, args...);
+}
 
 // phi_mm on the FmtH2 engine (TN = 4): phi_w1_kernel (one wave per SIMD, B
 // fragments straight from the image; phi_w1.hpp) -- on the full D layout (row
@@ -36,7 +46,8 @@ static void launch_w1(dim3 grid, hipStream_t s, Args... args) {
 // in order (deterministic, no atomics).
 // row0: interacting-set index of A's row 0 (EXP: the diagonal j == row0 + i
 // is skipped, see NNTile::store).
-template <int TN, bool EXP, int WM, int TM, int BJ, bool SWZB = true>
+// FAM: the kernel family of the EXP staging (common.hpp); IMQ: u^pw.
+template <int TN, bool EXP, int WM, int TM, int BJ, bool SWZB = true, int FAM = kFamRBF>
 __global__ __launch_bounds__(256 * WM) void nn_kernel(const float* __restrict__ A, int64_t a_npad,
                                                       const float* __restrict__ B, int64_t ldb,
                                                       int64_t K, int64_t kchunk,
@@ -44,10 +55,11 @@ __global__ __launch_bounds__(256 * WM) void nn_kernel(const float* __restrict__ 
                                                       float* __restrict__ C, int64_t ldc,
                                                       float* __restrict__ rowsum, int64_t m,
                                                       int64_t row0,
-                                                      const float* __restrict__ gate) {
+                                                      const float* __restrict__ gate,
+                                                      float pw = 0.f) {
   // gate: run iff *gate != 0 (the FmtH2 range guard when no FmtX3 image fits)
   if (gate && *gate == 0.f) return;
-  using Tile = NNTile<TN, EXP, WM, TM, BJ, SWZB>;
+  using Tile = NNTile<TN, EXP, WM, TM, BJ, SWZB, FAM>;
   __shared__ __attribute__((aligned(16))) float smem[Tile::kSmemFloats];
   const int64_t i0 = (int64_t)blockIdx.y * Tile::BM;
   const int64_t c0 = (int64_t)blockIdx.x * Tile::BC;
@@ -56,8 +68,9 @@ __global__ __launch_bounds__(256 * WM) void nn_kernel(const float* __restrict__ 
   C += (int64_t)blockIdx.z * m * ldc;
   if (rowsum) rowsum += (int64_t)blockIdx.z * roundup128(m);
   float scale = 0.f;
-  if (EXP) scale = -st->inv_h * kLog2e;
+  if (EXP) scale = FAM == kFamIMQ ? st->inv_h : -st->inv_h * kLog2e;
   Tile tile;
+  if constexpr (FAM == kFamIMQ) tile.pw = pw;
   tile.run(A + (i0 >> 7) * (a_npad >> 4) * kPanelElems + (i0 & 127) * 16, B + c0, ldb, k0, k1,
            scale, smem, row0 + i0);
 
@@ -92,7 +105,9 @@ __global__ __launch_bounds__(256 * WM) void nn_kernel(const float* __restrict__ 
 // F = FmtH2: C and rowsum come out of the MFMAs scaled by 2^15 (the A
 // staging scale) and C's column c by the B image's column scale: the stores
 // multiply by colinv[c] * 2^-15 (exact powers of two).
-template <int TN, bool DMA, bool EXP, bool M16, int RW = 2, class F = FmtX3, int NB = 2>
+// FAM: the kernel family of the EXP staging (common.hpp); IMQ: u^pw.
+template <int TN, bool DMA, bool EXP, bool M16, int RW = 2, class F = FmtX3, int NB = 2,
+          int FAM = kFamRBF>
 __global__ __launch_bounds__(512) void nn_x3_kernel(const float* __restrict__ A, int64_t a_npad,
                                                     const typename F::E* __restrict__ Yx,
                                                     int64_t ldy, int64_t K, int64_t kchunk,
@@ -102,10 +117,11 @@ __global__ __launch_bounds__(512) void nn_x3_kernel(const float* __restrict__ A,
                                                     int64_t row0, int sym,
                                                     const float* __restrict__ colinv,
                                                     int dsplit, int slice0,
-                                                    const float* __restrict__ gate, int gate_on) {
+                                                    const float* __restrict__ gate, int gate_on,
+                                                    float pw = 0.f) {
   // gate (the FmtH2 range guard, dsvgd_h2_scales): run iff *gate != 0 equals gate_on
   if (gate && ((*gate != 0.f) != (gate_on != 0))) return;
-  using Tile = NNX3Tile<TN, DMA, EXP, M16, RW, F, NB>;
+  using Tile = NNX3Tile<TN, DMA, EXP, M16, RW, F, NB, FAM>;
   __shared__ __attribute__((aligned(16))) char smem[Tile::kSmemBytes];
   // dsplit (symmetric layout, 128-row blocks): 1 = only the K-steps left of
   // the block's diagonal tile (the transposed ones), longest rows first; the
@@ -130,7 +146,8 @@ __global__ __launch_bounds__(512) void nn_x3_kernel(const float* __restrict__ A,
   }
   C += (int64_t)(slice0 + bz) * m * ldc;
   if (EXP) rowsum += (int64_t)(slice0 + bz) * roundup128(m);
-  const float scale = EXP ? -st->inv_h * kLog2e : 0.f;
+  const float scale = !EXP ? 0.f : FAM == kFamIMQ ? st->inv_h : -st->inv_h * kLog2e;
+  if constexpr (FAM == kFamIMQ) tile.pw = pw;
   tile.prow = (a_npad >> 4) * kPanelElems * 4;
   if (DMA && sym) {  // symmetric layout: m == n, row0 == 0 (checked by the ABI)
     tile.sym_D = A;
@@ -255,34 +272,37 @@ static int xmap_ok(dim3 g, int bit) {
          ((int64_t)g.y * g.z) % 8 == 0;
 }
 
-template <int TN, bool EXP, class F>
+template <int TN, bool EXP, class F, int FAM = kFamRBF>
 int launch_nn_x3(const float* D, int64_t K, const typename F::E* Yx, int64_t ldy, int splits,
                  const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
                  int64_t row0, int sym, int m16, const float* colinv, hipStream_t s,
-                 const float* gate, int gate_on) {
+                 const float* gate, int gate_on, float pw = 0.f) {
   if (sym && TN == 1) return fail_arg("nn_x3: the symmetric layout needs ldy % 256 == 0");
   const int64_t kchunk = roundup((K + splits - 1) / splits, kX3Step);
   const dim3 grid(ldy / (128 * TN), roundup(m, 128) / 128, splits);
   if (F::P == 3 && m16 && TN == 1)
     return fail_arg("nn_x3: the 16x16 form needs the DMA path (ldy % 256 == 0)");
   if (TN == 1)  // TN = 1: 1.5 DMA rounds per K-step -> the register-staged form
-    hipLaunchKernelGGL((nn_x3_kernel<TN, false, EXP, false, 2, F>), grid, dim3(512), 0, s, D, K, Yx,
-                       ldy, K, kchunk, st, C, ldc, rowsum, m, row0, 0, colinv, 0, 0, gate, gate_on);
+    hipLaunchKernelGGL((nn_x3_kernel<TN, false, EXP, false, 2, F, 2, FAM>), grid, dim3(512), 0, s, D,
+                       K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, 0, colinv, 0, 0, gate,
+                       gate_on, pw);
   else if constexpr (F::P == 3) {
     if (m16)
-      hipLaunchKernelGGL((nn_x3_kernel<TN, TN != 1, EXP, TN != 1, 2, F>), grid, dim3(512), 0, s, D,
-                         K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, 0, 0, gate, gate_on);
+      hipLaunchKernelGGL((nn_x3_kernel<TN, TN != 1, EXP, TN != 1, 2, F, 2, FAM>), grid, dim3(512), 0,
+                         s, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, 0, 0,
+                         gate, gate_on, pw);
     else
-      hipLaunchKernelGGL((nn_x3_kernel<TN, TN != 1, EXP, false, 2, F>), grid, dim3(512), 0, s, D, K,
-                         Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, 0, 0, gate, gate_on);
+      hipLaunchKernelGGL((nn_x3_kernel<TN, TN != 1, EXP, false, 2, F, 2, FAM>), grid, dim3(512), 0,
+                         s, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, 0, 0,
+                         gate, gate_on, pw);
   } else {  // FmtH2: the smaller stages fit a 3-stage ring
     if (TN == 4 && EXP && sym && splits >= 2 && g_phi_symrow) {
       // symmetric layout, each row's slices in ONE launch (phi_w1 DS 4):
       // contiguous K ranges walked ascending, transposed K-steps first; the
       // blocks of an XCD share a slice (xmap: 8 | row blocks x slices)
       const bool xmap = xmap_ok(grid, 1);
-      launch_w1<4>(grid, s, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, 0,
-                   gate, gate_on, 0, 0, 0, xmap ? 1 : 0);
+      launch_w1k<4, FAM>(grid, s, pw, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym,
+                         colinv, 0, gate, gate_on, 0, 0, 0, xmap ? 1 : 0, 0, 1, (int64_t)0);
       return check_launch("phi_w1_kernel(rows)");
     }
     if (TN == 4 && EXP && sym && splits >= 2) {
@@ -298,39 +318,50 @@ int launch_nn_x3(const float* D, int64_t K, const typename F::E* Yx, int64_t ldy
         return fail_arg("phi_mm: the hybrid's split-K chains would exceed 2 x 16384 columns; "
                         "size the slices with dsvgd_phi_splits_sym under the current symrow form");
       const dim3 g1(grid.x, grid.y, sl), g2(grid.x, grid.y, splits - sl);
-      launch_w1<1>(g1, s, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, 0,
-                   gate, gate_on);
+      launch_w1k<1, FAM>(g1, s, pw, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym,
+                         colinv, 0, gate, gate_on, 0, 0, 0, 0, 0, 1, (int64_t)0);
       const int rc = check_launch("phi_w1_kernel(lower)");
       if (rc) return rc;
-      launch_w1<2>(g2, s, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, sl,
-                   gate, gate_on);
+      launch_w1k<2, FAM>(g2, s, pw, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym,
+                         colinv, sl, gate, gate_on, 0, 0, 0, 0, 0, 1, (int64_t)0);
       return check_launch("phi_w1_kernel(upper)");
     }
     if (TN == 4 && EXP && !sym) {
-      launch_w1<0>(grid, s, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym, colinv, 0,
-                   gate, gate_on, 0, 0, 0, xmap_ok(grid, 2));
+      launch_w1k<0, FAM>(grid, s, pw, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym,
+                         colinv, 0, gate, gate_on, 0, 0, 0, xmap_ok(grid, 2), 0, 1, (int64_t)0);
       return check_launch("phi_w1_kernel");
     }
-    hipLaunchKernelGGL((nn_x3_kernel<TN, TN != 1, EXP, false, 2, F, TN != 1 ? 3 : 2>), grid,
+    hipLaunchKernelGGL((nn_x3_kernel<TN, TN != 1, EXP, false, 2, F, TN != 1 ? 3 : 2, FAM>), grid,
                        dim3(512), 0, s, D, K, Yx, ldy, K, kchunk, st, C, ldc, rowsum, m, row0, sym,
-                       colinv, 0, 0, gate, gate_on);
+                       colinv, 0, 0, gate, gate_on, pw);
   }
   return check_launch("nn_x3_kernel");
 }
 
 // C = f(A) B on the split engine; A panel layout (m_pad x K), B = Yx image
 // (K rows, ldy columns, a multiple of 128).  exp_: the phi_mm form.
-template <class F>
+// FAM = IMQ (exp_ only): the staging is u^pw (common.hpp imq_pow).
+template <class F, int FAM = kFamRBF>
 int nn_split_gemm(bool exp_, const float* A, int64_t K, const typename F::E* Yx, int64_t ldy,
                   int splits, const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum,
                   int64_t m, int64_t row0, hipStream_t s, int sym, int m16, const float* colinv,
-                  const float* gate = nullptr, int gate_on = 0) {
+                  const float* gate = nullptr, int gate_on = 0, float pw = 0.f) {
   if (F::P == 2) m16 = 0;  // the fp16 format runs the 32x32x16 form
   // buffer offsets are 32-bit: K rows x ldy columns x P parts x 2 bytes of
   // the image (as dsvgd_phi_mm_{h2,x3} check), K x 128 x 4 bytes of D
   if (K * ldy * 2 * F::P >= ((int64_t)1 << 31) || K * 128 * 4 >= ((int64_t)1 << 31))
     return fail_arg("nn_x3: K x ldy too large for 32-bit buffer offsets");
   if (ldy % 128 != 0) return fail_arg("nn_x3: ldy must be a multiple of 128");
+  if constexpr (FAM == kFamIMQ) {
+    if (!exp_) return fail_arg("nn_x3: the IMQ staging is the exp form's");
+#define DSVGD_X3_TN(TN)                                                                          \
+  return launch_nn_x3<TN, true, F, FAM>(A, K, Yx, ldy, splits, st, C, ldc, rowsum, m, row0, sym, \
+                                        m16, colinv, s, gate, gate_on, pw)
+    if (ldy % 512 == 0) DSVGD_X3_TN(4);
+    if (ldy % 256 == 0) DSVGD_X3_TN(2);
+    DSVGD_X3_TN(1);
+#undef DSVGD_X3_TN
+  }
   if constexpr (F::P == 2) {
     if (!exp_ && ldy % 512 != 0 && ldy % 256 == 0 && g_gxd_w1) {
       // G . Xd on phi_w1's shape: 128-row x 256-column blocks of four waves
@@ -419,6 +450,24 @@ int nn_h2_gemm(bool exp_, const float* A, int64_t K, const _Float16* Yh, int64_t
                int64_t row0, hipStream_t s, int sym, const float* colinv, const float* gate) {
   return nn_split_gemm<FmtH2>(exp_, A, K, Yh, ldy, splits, st, C, ldc, rowsum, m, row0, s, sym, 0,
                               colinv, gate, 0);
+}
+
+// phi_mm's two split engines with the IMQ staging K = u^pw, u = 1 + D/h (pw =
+// beta: F, pw = beta - 1: G'); everything else as the two above with exp_.
+static int nn_x3_gemm_imq(const float* A, int64_t K, const __bf16* Yx, int64_t ldy, int splits,
+                          const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum,
+                          int64_t m, int64_t row0, hipStream_t s, int sym, int m16,
+                          const float* gate, float pw) {
+  return nn_split_gemm<FmtX3, kFamIMQ>(true, A, K, Yx, ldy, splits, st, C, ldc, rowsum, m, row0, s,
+                                       sym, m16, nullptr, gate, 1, pw);
+}
+
+static int nn_h2_gemm_imq(const float* A, int64_t K, const _Float16* Yh, int64_t ldy, int splits,
+                          const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum,
+                          int64_t m, int64_t row0, hipStream_t s, int sym, const float* colinv,
+                          const float* gate, float pw) {
+  return nn_split_gemm<FmtH2, kFamIMQ>(true, A, K, Yh, ldy, splits, st, C, ldc, rowsum, m, row0, s,
+                                       sym, 0, colinv, gate, 0, pw);
 }
 
 
@@ -578,6 +627,74 @@ __global__ __launch_bounds__(256) void phi_finish_w_kernel(
   }
 }
 
+// phi_finish of the IMQ kernel k = u^beta, u = 1 + D/h: two runs of the
+// two-operand phi_mm left KF = [F Xc | F S] (F = u^beta) and KG = [G' Xc | G' S]
+// with the row sums rG (G' = u^(beta-1)), `splits` slices each, summed here in
+// slice order:
+//   phi[i][c] = inv_n ((s_i + FS) + c1 (rG_i xc_i - G'Xc)) [+ extra[i][c]],
+//   c1 = -2 beta / h (grad_x k = c1 G' (x - y) = -grad_y k; the self term is s_i).
+// V: columns per thread (4: 16-byte accesses, every stride and base aligned;
+// the same bits as 1).
+template <int V>
+__global__ __launch_bounds__(256) void phi_finish_imq_kernel(
+    const float* __restrict__ KF, int64_t ldkf, const float* __restrict__ KG, int64_t ldkg,
+    const float* __restrict__ rowsum, int splits, const float* __restrict__ Y, int64_t ldy,
+    int64_t row0, int64_t m, int64_t dv, int64_t dp, const dsvgd_select_state* __restrict__ st,
+    float beta, float inv_n, float step, const float* __restrict__ extra, int64_t lde,
+    float* __restrict__ phi, int64_t ldphi, float* __restrict__ X, int64_t ldx) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= m * dv) return;
+  const int64_t i = t / dv, c = (t % dv) * V;
+  const float c1 = -2.f * beta * st->inv_h;
+  const int64_t mp = roundup128(m);
+  auto ld = [](const float* q, float (&o)[V]) {
+    if constexpr (V == 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = v[e];
+    } else {
+      o[0] = q[0];
+    }
+  };
+  auto stv = [](float* q, const float (&o)[V]) {
+    if constexpr (V == 4)
+      *reinterpret_cast<f32x4*>(q) = f32x4{o[0], o[1], o[2], o[3]};
+    else
+      q[0] = o[0];
+  };
+  const float* yi = Y + (row0 + i) * ldy;
+  float yx[V], ys[V], p[V], fs[V] = {}, gx[V] = {}, a[V], b[V];
+  ld(yi + c, yx);
+  ld(yi + dp + c, ys);
+  float r = 0.f;
+  for (int z = 0; z < splits; ++z) {
+    ld(KF + ((int64_t)z * m + i) * ldkf + dp + c, a);
+    ld(KG + ((int64_t)z * m + i) * ldkg + c, b);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      fs[e] += a[e];
+      gx[e] += b[e];
+    }
+    r += rowsum[(int64_t)z * mp + i];
+  }
+#pragma unroll
+  for (int e = 0; e < V; ++e) p[e] = inv_n * ((ys[e] + fs[e]) + c1 * (r * yx[e] - gx[e]));
+  if (extra) {
+    float ex[V];
+    ld(extra + i * lde + c, ex);
+#pragma unroll
+    for (int e = 0; e < V; ++e) p[e] += ex[e];
+  }
+  if (phi) stv(phi + i * ldphi + c, p);
+  if (X) {
+    float x[V];
+    ld(X + i * ldx + c, x);
+#pragma unroll
+    for (int e = 0; e < V; ++e) x[e] += step * p[e];
+    stv(X + i * ldx + c, x);
+  }
+}
+
 // ---- split-K partials summed (dsvgd_phi_h2_transposed, the wide sweep) ---
 // out[i][c] = sum_z P[z][i][c], out_rs[i] = sum_z rs[z][i] in a fixed order:
 // a workgroup takes 256 / G float4 positions; its G thread groups (G = the
@@ -688,21 +805,26 @@ __global__ __launch_bounds__(256) void phi_finish_parts_kernel(
 // exceeds the 1e-5 tolerance).  Block: 64 rows x 64 columns; thread (rq, cq)
 // owns rows 4rq..+3 x columns 4cq..+3; j streams in chunks of 64 through LDS
 // (K chunk transposed [j][i], x_j and s_j [j][c]).  VALU: 3 ops per (i,j,c).
+// FAM = IMQ: k_ij s_j -> F_ij s_j and (2/h) k_ij -> c1 G'_ij, c1 = -2 beta / h
+// (F = u^beta, G' = u^(beta-1), u = 1 + D/h); c1 G' in a second LDS chunk.
 constexpr int kPhiDirectMaxD = 64;
 
+template <int FAM = kFamRBF>
 __global__ __launch_bounds__(256) void phi_direct_kernel(
     const float* __restrict__ D, int64_t n_pad, const float* __restrict__ Y, int64_t ldy,
     int64_t row0, int64_t m, int64_t n, int d, int64_t dp,
     const dsvgd_select_state* __restrict__ st, float inv_n, float step,
     const float* __restrict__ extra, int64_t lde, float* __restrict__ phi, int64_t ldphi,
-    float* __restrict__ X, int64_t ldx, int64_t jchunk, float* __restrict__ part) {
+    float* __restrict__ X, int64_t ldx, int64_t jchunk, float* __restrict__ part,
+    float beta = 0.f) {
   __shared__ __attribute__((aligned(16))) float kT[64][64];
+  __shared__ __attribute__((aligned(16))) float gT[FAM == kFamIMQ ? 64 : 1][64];
   __shared__ __attribute__((aligned(16))) float xs[64][64];
   __shared__ __attribute__((aligned(16))) float ss[64][64];
   const int t = threadIdx.x, rq = t >> 4, cq = t & 15;
   const int64_t i0 = (int64_t)blockIdx.x * 64;
   const float inv_h = st->inv_h;
-  const float scale = -inv_h * kLog2e, g = 2.f * inv_h;
+  const float scale = -inv_h * kLog2e, g = FAM == kFamIMQ ? -2.f * beta * inv_h : 2.f * inv_h;
   float xi[4][4], acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -736,7 +858,14 @@ __global__ __launch_bounds__(256) void phi_direct_kernel(
     for (int e = t; e < 64 * 64; e += 256) {
       const int r = e >> 6, q = e & 63;  // kT[q][r]: row i0+r, column j0+q
       const int64_t i = i0 + r, j = j0 + q;
-      kT[q][r] = (i < m && j < je) ? __builtin_amdgcn_exp2f(D[panel_off(i, j, n_pad)] * scale) : 0.f;
+      if constexpr (FAM == kFamIMQ) {
+        const bool ok = i < m && j < je;
+        const float lg = ok ? __builtin_amdgcn_logf(fmaf(D[panel_off(i, j, n_pad)], inv_h, 1.f)) : 0.f;
+        kT[q][r] = ok ? __builtin_amdgcn_exp2f(beta * lg) : 0.f;
+        gT[q][r] = ok ? g * __builtin_amdgcn_exp2f((beta - 1.f) * lg) : 0.f;
+      } else {
+        kT[q][r] = (i < m && j < je) ? __builtin_amdgcn_exp2f(D[panel_off(i, j, n_pad)] * scale) : 0.f;
+      }
       const int64_t jr = j0 + r;
       xs[r][q] = (jr < je && q < d) ? Y[jr * ldy + q] : 0.f;
       ss[r][q] = (jr < je && q < d) ? Y[jr * ldy + dp + q] : 0.f;
@@ -747,10 +876,19 @@ __global__ __launch_bounds__(256) void phi_direct_kernel(
       const f32x4 k4 = *reinterpret_cast<const f32x4*>(&kT[q][4 * rq]);
       const f32x4 x4 = *reinterpret_cast<const f32x4*>(&xs[q][4 * cq]);
       const f32x4 s4 = *reinterpret_cast<const f32x4*>(&ss[q][4 * cq]);
+      if constexpr (FAM == kFamIMQ) {
+        const f32x4 g4 = *reinterpret_cast<const f32x4*>(&gT[q][4 * rq]);
 #pragma unroll
-      for (int a = 0; a < 4; ++a)
+        for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) acc[a][c] = fmaf(k4[a], fmaf(g, xi[a][c] - x4[c], s4[c]), acc[a][c]);
+          for (int c = 0; c < 4; ++c)
+            acc[a][c] = fmaf(g4[a], xi[a][c] - x4[c], fmaf(k4[a], s4[c], acc[a][c]));
+      } else {
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[a][c] = fmaf(k4[a], fmaf(g, xi[a][c] - x4[c], s4[c]), acc[a][c]);
+      }
     }
     __syncthreads();
   }
@@ -813,18 +951,31 @@ __device__ __forceinline__ void group_reduce(float* red, int dc, int G) {
 // partials per column are added in group order (deterministic).  At the
 // reference's small d (1-3) that keeps the whole block busy instead of d
 // threads walking every j.
+// FAM = IMQ: a second per-column coefficient, k_j -> F_j = u^beta on s_j and
+// gb_j = c1 G'_j = (-2 beta / h) u^(beta-1) on (x_i - x_j), u = 1 + |x_i - x_j|^2/h.
+template <int FAM>
+__device__ __forceinline__ void imq_row_coef(float s2, float inv_h, float beta, float& k,
+                                             float& gk) {
+  const float lg = log2f(fmaf(s2, inv_h, 1.f));
+  k = exp2f(beta * lg);
+  gk = -2.f * beta * inv_h * exp2f((beta - 1.f) * lg);
+}
+
+template <int FAM = kFamRBF>
 __global__ __launch_bounds__(256) void phi_row_kernel(float* __restrict__ X, int64_t ldx,
                                                       const float* __restrict__ S, int64_t lds,
                                                       int64_t n, int64_t d, int64_t i,
                                                       const dsvgd_select_state* __restrict__ st,
                                                       float step,
                                                       const float* __restrict__ extra,
-                                                      float* __restrict__ phi_out) {
+                                                      float* __restrict__ phi_out,
+                                                      float beta = 0.f) {
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   float* xi = dyn;            // d
   float* acc = dyn + d;       // d
   float* kb = dyn + 2 * d;    // 256
   float* red = kb + 256;      // 256
+  float* gb = red + 256;      // 256 (IMQ only)
   const int t = threadIdx.x;
   const float inv_h = st->inv_h;
   const float g2 = 2.f * inv_h;
@@ -835,16 +986,20 @@ __global__ __launch_bounds__(256) void phi_row_kernel(float* __restrict__ X, int
   __syncthreads();
   for (int64_t j0 = 0; j0 < n; j0 += 256) {
     const int64_t j = j0 + t;
-    float k = 0.f;
+    float k = 0.f, gk = 0.f;
     if (j < n) {
       float s2 = 0.f;
       for (int64_t c = 0; c < d; ++c) {
         const float df = X[j * ldx + c] - xi[c];
         s2 = fmaf(df, df, s2);
       }
-      k = expf(-s2 * inv_h);
+      if constexpr (FAM == kFamIMQ)
+        imq_row_coef<FAM>(s2, inv_h, beta, k, gk);
+      else
+        k = expf(-s2 * inv_h);
     }
     kb[t] = k;
+    if constexpr (FAM == kFamIMQ) gb[t] = gk;
     __syncthreads();
     const int nj = (int)min((int64_t)256, n - j0);
     for (int64_t c0 = 0; c0 < d; c0 += 256) {
@@ -856,7 +1011,10 @@ __global__ __launch_bounds__(256) void phi_row_kernel(float* __restrict__ X, int
         const float x = xi[c];
         for (int q = t / dc; q < nj; q += G) {
           const int64_t jj = j0 + q;
-          part = fmaf(kb[q], fmaf(g2, x - X[jj * ldx + c], S[jj * lds + c]), part);
+          if constexpr (FAM == kFamIMQ)
+            part = fmaf(gb[q], x - X[jj * ldx + c], fmaf(kb[q], S[jj * lds + c], part));
+          else
+            part = fmaf(kb[q], fmaf(g2, x - X[jj * ldx + c], S[jj * lds + c]), part);
         }
       }
       red[t] = part;
@@ -884,18 +1042,20 @@ __global__ __launch_bounds__(256) void phi_row_kernel(float* __restrict__ X, int
 // the phi_row_kernel column/group split) into partial[b][c].
 // phi_row_finish_kernel adds the partials in block order (deterministic) and
 // moves x_i.  VEC: ldx % 4 == 0 and a 16-byte aligned X.
-template <bool VEC>
+template <bool VEC, int FAM = kFamRBF>
 __global__ __launch_bounds__(256) void phi_row_part_kernel(const float* __restrict__ X,
                                                            int64_t ldx,
                                                            const float* __restrict__ S,
                                                            int64_t lds, int64_t n, int64_t d,
                                                            int64_t i, int64_t J,
                                                            const dsvgd_select_state* __restrict__ st,
-                                                           float* __restrict__ partial) {
+                                                           float* __restrict__ partial,
+                                                           float beta = 0.f) {
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   float* xi = dyn;         // roundup(d, 4)
   float* red = dyn + ((d + 3) & ~(int64_t)3);  // 256
   float* kb = red + 256;   // J
+  float* gb = kb + J;      // J (IMQ only)
   const int t = threadIdx.x;
   const float inv_h = st->inv_h;
   const float g2 = 2.f * inv_h;
@@ -921,7 +1081,11 @@ __global__ __launch_bounds__(256) void phi_row_part_kernel(const float* __restri
       }
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
-      if (j < j1 && l16 == 0) kb[j - j0] = expf(-s2 * inv_h);
+      if constexpr (FAM == kFamIMQ) {
+        if (j < j1 && l16 == 0) imq_row_coef<FAM>(s2, inv_h, beta, kb[j - j0], gb[j - j0]);
+      } else {
+        if (j < j1 && l16 == 0) kb[j - j0] = expf(-s2 * inv_h);
+      }
     }
   } else {
     for (int64_t j = j0 + t; j < j1; j += 256) {
@@ -930,7 +1094,10 @@ __global__ __launch_bounds__(256) void phi_row_part_kernel(const float* __restri
         const float df = X[j * ldx + c] - xi[c];
         s2 = fmaf(df, df, s2);
       }
-      kb[j - j0] = expf(-s2 * inv_h);
+      if constexpr (FAM == kFamIMQ)
+        imq_row_coef<FAM>(s2, inv_h, beta, kb[j - j0], gb[j - j0]);
+      else
+        kb[j - j0] = expf(-s2 * inv_h);
     }
   }
   __syncthreads();
@@ -944,7 +1111,10 @@ __global__ __launch_bounds__(256) void phi_row_part_kernel(const float* __restri
       const float x = xi[c];
       for (int q = t / dc; q < nj; q += G) {
         const int64_t jj = j0 + q;
-        part = fmaf(kb[q], fmaf(g2, x - X[jj * ldx + c], S[jj * lds + c]), part);
+        if constexpr (FAM == kFamIMQ)
+          part = fmaf(gb[q], x - X[jj * ldx + c], fmaf(kb[q], S[jj * lds + c], part));
+        else
+          part = fmaf(kb[q], fmaf(g2, x - X[jj * ldx + c], S[jj * lds + c]), part);
       }
     }
     red[t] = part;
@@ -992,14 +1162,19 @@ __global__ __launch_bounds__(256) void phi_row_finish_kernel(float* __restrict__
 // NN block shape: 128 rows x 128*TN columns, 8 waves (2 per SIMD, 128
 // accumulators each); K-steps of 32 columns (two D panels per barrier,
 // 160 KiB LDS, XOR-swizzled A image) when K allows, else 16.
-template <int TN, int BJ>
+template <int TN, int BJ, int FAM = kFamRBF>
 int launch_nn_shape(bool exp_, const float* A, const float* B, int64_t ldb, int64_t K, int splits,
                     const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
-                    int64_t cols, int64_t row0, hipStream_t s, const float* gate) {
+                    int64_t cols, int64_t row0, hipStream_t s, const float* gate, float pw = 0.f) {
   constexpr int WM = 2, TM = 2, BM = 32 * TM * WM;
   if (K % BJ != 0) return fail_arg("nn_kernel: K must be a multiple of the K-step");
   const int64_t kchunk = roundup((K + splits - 1) / splits, BJ);
   const dim3 grid(cols / (128 * TN), roundup(m, BM) / BM, splits);
+  if constexpr (FAM == kFamIMQ) {  // (exp_ only: the staging is u^pw)
+    hipLaunchKernelGGL((nn_kernel<TN, true, WM, TM, BJ, true, FAM>), grid, dim3(256 * WM), 0, s, A,
+                       K, B, ldb, K, kchunk, st, C, ldc, rowsum, m, row0, gate, pw);
+    return check_launch("nn_kernel(imq)");
+  }
   if (exp_)
     hipLaunchKernelGGL((nn_kernel<TN, true, WM, TM, BJ>), grid, dim3(256 * WM), 0, s, A, K, B, ldb,
                        K, kchunk, st, C, ldc, rowsum, m, row0, gate);
@@ -1009,15 +1184,15 @@ int launch_nn_shape(bool exp_, const float* A, const float* B, int64_t ldb, int6
   return check_launch("nn_kernel");
 }
 
-template <int TN>
+template <int TN, int FAM = kFamRBF>
 int launch_nn(bool exp_, const float* A, const float* B, int64_t ldb, int64_t K, int splits,
               const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
-              int64_t cols, int64_t row0, hipStream_t s, const float* gate) {
+              int64_t cols, int64_t row0, hipStream_t s, const float* gate, float pw = 0.f) {
   if (K % 32 == 0)  // split-K chunks are rounded to the K-step
-    return launch_nn_shape<TN, 32>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0,
-                                   s, gate);
-  return launch_nn_shape<TN, 16>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s,
-                                 gate);
+    return launch_nn_shape<TN, 32, FAM>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols,
+                                        row0, s, gate, pw);
+  return launch_nn_shape<TN, 16, FAM>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0,
+                                      s, gate, pw);
 }
 
 // C[splits x m x cols] = f(A) B with A in panel layout (m_pad x K), B row-major K x cols.
@@ -1035,6 +1210,24 @@ int nn_gemm(bool exp_, const float* A, int64_t K, const float* B, int64_t ldb, i
   if (cols % 256 == 0)
     return launch_nn<2>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s, gate);
   return launch_nn<1>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s, gate);
+}
+
+// nn_gemm's exp form with the IMQ staging K = u^pw (the exact f32 engine)
+static int nn_gemm_imq(const float* A, int64_t K, const float* B, int64_t ldb, int64_t cols,
+                       int splits, const dsvgd_select_state* st, float* C, int64_t ldc,
+                       float* rowsum, int64_t m, int64_t row0, hipStream_t s, const float* gate,
+                       float pw) {
+  if (K * ldb * (int64_t)sizeof(float) >= ((int64_t)1 << 31) ||
+      K * 128 * (int64_t)sizeof(float) >= ((int64_t)1 << 31))
+    return fail_arg("nn_kernel: K x ldb too large for 32-bit buffer offsets (split the columns)");
+  if (cols % 512 == 0)
+    return launch_nn<4, kFamIMQ>(true, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s,
+                                 gate, pw);
+  if (cols % 256 == 0)
+    return launch_nn<2, kFamIMQ>(true, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s,
+                                 gate, pw);
+  return launch_nn<1, kFamIMQ>(true, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s,
+                               gate, pw);
 }
 
 // split-K slices: (1) enough for >= 2 blocks per CU (256 CUs) when the owned
@@ -1221,6 +1414,89 @@ int dsvgd_phi_mm_h2(const float* D, int64_t ldd, const void* Yh, int64_t ldy, in
                 "sym: the symmetric layout needs m == n, row0 == 0, ldy % 256 == 0");
   return nn_h2_gemm(true, D, n_pad, (const _Float16*)Yh, ldy, (int)splits, st, KY, ldk, rowsum, m,
                     row0, (hipStream_t)stream, sym, colinv, gate);
+}
+
+// ---- phi_mm with a kernel description (include/dsvgd.h) -------------------
+// RBF: the entry point beside it; IMQ: the same checks, the u^pw staging with
+// pw = beta (order 0: F) or beta - 1 (order 1: G').
+static bool kern_ok(dsvgd_kernel k) {
+  return k.family == DSVGD_KERNEL_RBF ||
+         (k.family == DSVGD_KERNEL_IMQ && k.beta >= -1.f && k.beta < 0.f);
+}
+#define DSVGD_REQUIRE_KERN(kern, order)                                                       \
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");              \
+  DSVGD_REQUIRE((order) == 0 || ((order) == 1 && (kern).family == DSVGD_KERNEL_IMQ),          \
+                "order: 0, or 1 (the gradient's matrix G') for the IMQ family")
+
+int dsvgd_phi_mm_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                      int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
+                      float* KY, int64_t ldk, float* rowsum, const float* gate,
+                      dsvgd_kernel kern, int order, void* stream) {
+  DSVGD_REQUIRE_KERN(kern, order);
+  if (kern.family == DSVGD_KERNEL_RBF)
+    return gate ? dsvgd_phi_mm_gated(D, ldd, Y, ldy, row0, m, n, st, splits, KY, ldk, rowsum, gate,
+                                     stream)
+                : dsvgd_phi_mm(D, ldd, Y, ldy, row0, m, n, st, splits, KY, ldk, rowsum, stream);
+  DSVGD_REQUIRE(D && Y && st && KY && rowsum, "null pointer");
+  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
+  const int64_t n_pad = roundup(n, 128);
+  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
+  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
+  DSVGD_REQUIRE(((uintptr_t)Y & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
+  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
+  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
+  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
+  return nn_gemm_imq(D, n_pad, Y, ldy, ldy, (int)splits, st, KY, ldk, rowsum, m, row0,
+                     (hipStream_t)stream, gate, kern.beta - (float)order);
+}
+
+int dsvgd_phi_mm_x3_kern(const float* D, int64_t ldd, const void* Yx, int64_t ldy, int64_t row0,
+                         int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
+                         float* KY, int64_t ldk, float* rowsum, int sym, int m16,
+                         const float* gate, dsvgd_kernel kern, int order, void* stream) {
+  DSVGD_REQUIRE_KERN(kern, order);
+  if (kern.family == DSVGD_KERNEL_RBF)
+    return dsvgd_phi_mm_x3(D, ldd, Yx, ldy, row0, m, n, st, splits, KY, ldk, rowsum, sym, m16, gate,
+                           stream);
+  DSVGD_REQUIRE(D && Yx && st && KY && rowsum, "null pointer");
+  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
+  const int64_t n_pad = roundup(n, 128);
+  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
+  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
+  DSVGD_REQUIRE(((uintptr_t)Yx & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
+  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
+  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
+  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
+  DSVGD_REQUIRE(n_pad * ldy * 6 < ((int64_t)1 << 31) && n_pad * 128 * 4 < ((int64_t)1 << 31),
+                "n x ldy too large for 32-bit buffer offsets (use dsvgd_phi_mm_kern)");
+  DSVGD_REQUIRE(!sym || (m == n && row0 == 0), "sym: the symmetric layout needs m == n, row0 == 0");
+  return nn_x3_gemm_imq(D, n_pad, (const __bf16*)Yx, ldy, (int)splits, st, KY, ldk, rowsum, m, row0,
+                        (hipStream_t)stream, sym, m16, gate, kern.beta - (float)order);
+}
+
+int dsvgd_phi_mm_h2_kern(const float* D, int64_t ldd, const void* Yh, int64_t ldy, int64_t row0,
+                         int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
+                         float* KY, int64_t ldk, float* rowsum, int sym, const float* colinv,
+                         const float* gate, dsvgd_kernel kern, int order, void* stream) {
+  DSVGD_REQUIRE_KERN(kern, order);
+  if (kern.family == DSVGD_KERNEL_RBF)
+    return dsvgd_phi_mm_h2(D, ldd, Yh, ldy, row0, m, n, st, splits, KY, ldk, rowsum, sym, colinv,
+                           gate, stream);
+  DSVGD_REQUIRE(D && Yh && st && KY && rowsum && colinv, "null pointer");
+  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
+  const int64_t n_pad = roundup(n, 128);
+  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
+  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
+  DSVGD_REQUIRE(((uintptr_t)Yh & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
+  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
+  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
+  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
+  DSVGD_REQUIRE(n_pad * ldy * 4 < ((int64_t)1 << 31) && n_pad * 128 * 4 < ((int64_t)1 << 31),
+                "n x ldy too large for 32-bit buffer offsets (use dsvgd_phi_mm_kern)");
+  DSVGD_REQUIRE(!sym || (m == n && row0 == 0 && ldy % 256 == 0),
+                "sym: the symmetric layout needs m == n, row0 == 0, ldy % 256 == 0");
+  return nn_h2_gemm_imq(D, n_pad, (const _Float16*)Yh, ldy, (int)splits, st, KY, ldk, rowsum, m,
+                        row0, (hipStream_t)stream, sym, colinv, gate, kern.beta - (float)order);
 }
 
 int dsvgd_phi_mm_h2w(const float* D, int64_t ldd, const void* Wh, int64_t ldw, int64_t row0,
@@ -1477,11 +1753,43 @@ int dsvgd_phi_finish_w(const float* KW, int64_t ldk, const float* rowsum, int64_
   return check_launch("phi_finish_w");
 }
 
-int dsvgd_phi_direct(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
-                     int64_t m, int64_t n, int64_t d, const dsvgd_select_state* st, float inv_n,
-                     float step, const float* extra, int64_t lde, float* phi, int64_t ldphi,
-                     float* X, int64_t ldx, float* partial, int64_t partial_floats,
-                     void* stream) {
+int dsvgd_phi_finish_imq(const float* KF, int64_t ldkf, const float* KG, int64_t ldkg,
+                         const float* rowsum, int64_t splits, const float* Y, int64_t ldy,
+                         int64_t row0, int64_t m, int64_t d, int64_t dp,
+                         const dsvgd_select_state* st, dsvgd_kernel kern, float inv_n, float step,
+                         const float* extra, int64_t lde, float* phi, int64_t ldphi, float* X,
+                         int64_t ldx, void* stream) {
+  DSVGD_REQUIRE(KF && KG && rowsum && Y && st, "null pointer");
+  DSVGD_REQUIRE(kern.family == DSVGD_KERNEL_IMQ && kern_ok(kern),
+                "kern: the IMQ family with beta in [-1, 0)");
+  DSVGD_REQUIRE(!extra || lde >= d, "lde");
+  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
+  DSVGD_REQUIRE(m > 0 && d > 0 && dp >= d && ldkf >= 2 * dp && ldkg >= 2 * dp && ldy >= 2 * dp,
+                "sizes");
+  DSVGD_REQUIRE(!phi || ldphi >= d, "ldphi");
+  DSVGD_REQUIRE(!X || ldx >= d, "ldx");
+  auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+#define DSVGD_FINISH_IMQ(V, DV)                                                                  \
+  hipLaunchKernelGGL((phi_finish_imq_kernel<V>), dim3((unsigned)((m * (DV) + 255) / 256)),        \
+                     dim3(256), 0, (hipStream_t)stream, KF, ldkf, KG, ldkg, rowsum, (int)splits, \
+                     Y, ldy, row0, m, DV, dp, st, kern.beta, inv_n, step, extra, lde, phi, ldphi, \
+                     X, ldx)
+  if (d % 4 == 0 && dp % 4 == 0 && ldkf % 4 == 0 && ldkg % 4 == 0 && ldy % 4 == 0 && a16(KF) &&
+      a16(KG) && a16(Y) && (!extra || (lde % 4 == 0 && a16(extra))) &&
+      (!phi || (ldphi % 4 == 0 && a16(phi))) && (!X || (ldx % 4 == 0 && a16(X)))) {
+    DSVGD_FINISH_IMQ(4, d / 4);
+    return check_launch("phi_finish_imq4");
+  }
+  DSVGD_FINISH_IMQ(1, d);
+#undef DSVGD_FINISH_IMQ
+  return check_launch("phi_finish_imq");
+}
+
+static int phi_direct_impl(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                           int64_t m, int64_t n, int64_t d, const dsvgd_select_state* st,
+                           float inv_n, float step, const float* extra, int64_t lde, float* phi,
+                           int64_t ldphi, float* X, int64_t ldx, float* partial,
+                           int64_t partial_floats, dsvgd_kernel kern, void* stream) {
   DSVGD_REQUIRE(D && Y && st, "null pointer");
   DSVGD_REQUIRE(!extra || lde >= d, "lde");
   DSVGD_REQUIRE(m > 0 && n > 0 && d > 0 && row0 >= 0, "sizes");
@@ -1505,14 +1813,38 @@ int dsvgd_phi_direct(const float* D, int64_t ldd, const float* Y, int64_t ldy, i
   nsplit = (n + jchunk - 1) / jchunk;
   float* part = nsplit > 1 ? partial : nullptr;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(phi_direct_kernel, dim3((unsigned)rb, (unsigned)nsplit), dim3(256), 0, s, D,
-                     n_pad, Y, ldy, row0, m, n, (int)d, dp, st, inv_n, step, extra, lde, phi, ldphi,
-                     X, ldx, jchunk, part);
+  if (kern.family == DSVGD_KERNEL_IMQ)
+    hipLaunchKernelGGL(phi_direct_kernel<kFamIMQ>, dim3((unsigned)rb, (unsigned)nsplit), dim3(256),
+                       0, s, D, n_pad, Y, ldy, row0, m, n, (int)d, dp, st, inv_n, step, extra, lde,
+                       phi, ldphi, X, ldx, jchunk, part, kern.beta);
+  else
+    hipLaunchKernelGGL(phi_direct_kernel<kFamRBF>, dim3((unsigned)rb, (unsigned)nsplit), dim3(256),
+                       0, s, D, n_pad, Y, ldy, row0, m, n, (int)d, dp, st, inv_n, step, extra, lde,
+                       phi, ldphi, X, ldx, jchunk, part, 0.f);
   int rc = check_launch("phi_direct");
   if (rc || !part) return rc;
   hipLaunchKernelGGL(phi_direct_finish_kernel, dim3((unsigned)((m * d + 255) / 256)), dim3(256), 0,
                      s, part, (int)nsplit, m, d, inv_n, step, extra, lde, phi, ldphi, X, ldx);
   return check_launch("phi_direct_finish");
+}
+
+int dsvgd_phi_direct(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                     int64_t m, int64_t n, int64_t d, const dsvgd_select_state* st, float inv_n,
+                     float step, const float* extra, int64_t lde, float* phi, int64_t ldphi,
+                     float* X, int64_t ldx, float* partial, int64_t partial_floats,
+                     void* stream) {
+  return phi_direct_impl(D, ldd, Y, ldy, row0, m, n, d, st, inv_n, step, extra, lde, phi, ldphi, X,
+                         ldx, partial, partial_floats, dsvgd_kernel{DSVGD_KERNEL_RBF, 0.f}, stream);
+}
+
+int dsvgd_phi_direct_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                          int64_t m, int64_t n, int64_t d, const dsvgd_select_state* st,
+                          float inv_n, float step, const float* extra, int64_t lde, float* phi,
+                          int64_t ldphi, float* X, int64_t ldx, float* partial,
+                          int64_t partial_floats, dsvgd_kernel kern, void* stream) {
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
+  return phi_direct_impl(D, ldd, Y, ldy, row0, m, n, d, st, inv_n, step, extra, lde, phi, ldphi, X,
+                         ldx, partial, partial_floats, kern, stream);
 }
 
 int dsvgd_phi_row(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n_int, int64_t d,
@@ -1522,9 +1854,24 @@ int dsvgd_phi_row(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n_
   DSVGD_REQUIRE(n_int > 0 && d > 0 && i >= 0 && i < n_int && ldx >= d && lds >= d, "sizes");
   DSVGD_REQUIRE(d <= 7936, "phi_row supports d <= 7936 (64 KiB LDS)");
   const size_t shm = (size_t)(2 * d + 512) * sizeof(float);
-  hipLaunchKernelGGL(phi_row_kernel, dim3(1), dim3(256), shm, (hipStream_t)stream, X, ldx, S, lds,
-                     n_int, d, i, st, step, extra, phi_out);
+  hipLaunchKernelGGL(phi_row_kernel<kFamRBF>, dim3(1), dim3(256), shm, (hipStream_t)stream, X, ldx,
+                     S, lds, n_int, d, i, st, step, extra, phi_out, 0.f);
   return check_launch("phi_row");
+}
+
+int dsvgd_phi_row_kern(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n_int,
+                       int64_t d, int64_t i, const dsvgd_select_state* st, float step,
+                       const float* extra, float* phi_out, dsvgd_kernel kern, void* stream) {
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
+  if (kern.family == DSVGD_KERNEL_RBF)
+    return dsvgd_phi_row(X, ldx, S, lds, n_int, d, i, st, step, extra, phi_out, stream);
+  DSVGD_REQUIRE(X && S && st, "null pointer");
+  DSVGD_REQUIRE(n_int > 0 && d > 0 && i >= 0 && i < n_int && ldx >= d && lds >= d, "sizes");
+  DSVGD_REQUIRE(d <= 7808, "phi_row (IMQ) supports d <= 7808 (64 KiB LDS)");
+  const size_t shm = (size_t)(2 * d + 768) * sizeof(float);
+  hipLaunchKernelGGL(phi_row_kernel<kFamIMQ>, dim3(1), dim3(256), shm, (hipStream_t)stream, X, ldx,
+                     S, lds, n_int, d, i, st, step, extra, phi_out, kern.beta);
+  return check_launch("phi_row(imq)");
 }
 
 int64_t dsvgd_phi_row_blocks(int64_t n, int64_t d) {
@@ -1537,20 +1884,38 @@ int64_t dsvgd_phi_row_blocks(int64_t n, int64_t d) {
 int dsvgd_phi_row_split(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n, int64_t d,
                         int64_t i, const dsvgd_select_state* st, float step, const float* extra,
                         float* phi_out, float* partial, int64_t blocks, void* stream) {
+  return dsvgd_phi_row_split_kern(X, ldx, S, lds, n, d, i, st, step, extra, phi_out, partial,
+                                  blocks, dsvgd_kernel{DSVGD_KERNEL_RBF, 0.f}, stream);
+}
+
+int dsvgd_phi_row_split_kern(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n,
+                             int64_t d, int64_t i, const dsvgd_select_state* st, float step,
+                             const float* extra, float* phi_out, float* partial, int64_t blocks,
+                             dsvgd_kernel kern, void* stream) {
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
+  const bool imq = kern.family == DSVGD_KERNEL_IMQ;
   DSVGD_REQUIRE(X && S && st && partial, "null pointer");
   DSVGD_REQUIRE(n > 0 && d > 0 && ldx >= d && lds >= d && i >= 0 && i < n, "sizes");
   DSVGD_REQUIRE(blocks >= 1 && blocks <= 65535, "blocks must be in [1, 65535]");
   DSVGD_REQUIRE(d <= 4096, "d <= 4096 (x_i is staged in LDS)");
   const int64_t J = (n + blocks - 1) / blocks;
-  const size_t shm = (size_t)(((d + 3) & ~(int64_t)3) + 256 + J) * sizeof(float);
+  // (IMQ: the second coefficient of each of the J rows)
+  const size_t shm = (size_t)(((d + 3) & ~(int64_t)3) + 256 + (imq ? 2 : 1) * J) * sizeof(float);
   DSVGD_REQUIRE(shm <= 64 * 1024, "rows per workgroup exceed the LDS budget (use more blocks)");
   hipStream_t s = (hipStream_t)stream;
-  if (ldx % 4 == 0 && ((uintptr_t)X & 15) == 0)
-    hipLaunchKernelGGL(phi_row_part_kernel<true>, dim3((unsigned)blocks), dim3(256), shm, s, X, ldx,
-                       S, lds, n, d, i, J, st, partial);
+  const bool vec = ldx % 4 == 0 && ((uintptr_t)X & 15) == 0;
+  if (imq && vec)
+    hipLaunchKernelGGL((phi_row_part_kernel<true, kFamIMQ>), dim3((unsigned)blocks), dim3(256), shm,
+                       s, X, ldx, S, lds, n, d, i, J, st, partial, kern.beta);
+  else if (imq)
+    hipLaunchKernelGGL((phi_row_part_kernel<false, kFamIMQ>), dim3((unsigned)blocks), dim3(256),
+                       shm, s, X, ldx, S, lds, n, d, i, J, st, partial, kern.beta);
+  else if (vec)
+    hipLaunchKernelGGL((phi_row_part_kernel<true>), dim3((unsigned)blocks), dim3(256), shm, s, X,
+                       ldx, S, lds, n, d, i, J, st, partial, 0.f);
   else
-    hipLaunchKernelGGL(phi_row_part_kernel<false>, dim3((unsigned)blocks), dim3(256), shm, s, X,
-                       ldx, S, lds, n, d, i, J, st, partial);
+    hipLaunchKernelGGL((phi_row_part_kernel<false>), dim3((unsigned)blocks), dim3(256), shm, s, X,
+                       ldx, S, lds, n, d, i, J, st, partial, 0.f);
   int rc = check_launch("phi_row_part");
   if (rc) return rc;
   hipLaunchKernelGGL(phi_row_finish_kernel, dim3(1), dim3(256), 0, s, X, ldx, n, d, i, partial,

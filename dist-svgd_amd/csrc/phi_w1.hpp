@@ -78,7 +78,11 @@ __device__ __forceinline__ f32x4 w1_load_nt(__amdgpu_buffer_rsrc_t r, int voff, 
 // per SIMD -- 128 accumulators leave room, and the second block's MFMAs are
 // what hides this block's staging VALU)
 constexpr int w1_waves(int NI, bool EXP) { return NI == 2 && EXP ? 2 : 1; }
-template <int DS, int NI = 4, bool EXP = true>
+// FAM: the kernel family of the staging (common.hpp); IMQ stages u^pw, pw a
+// launch argument (so F = u^beta and G' = u^(beta - 1) share an instantiation)
+// that only the IMQ instantiations have: PW is {float} there and empty for
+// the RBF, whose signature, argument block and code stay what they were.
+template <int DS, int NI = 4, bool EXP = true, int FAM = kFamRBF, class... PW>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(w1_waves(NI, EXP), w1_waves(NI, EXP)))) void phi_w1_kernel(
     const float* A, int64_t a_npad, const _Float16* Yx, int64_t ldy,
@@ -86,7 +90,9 @@ __attribute__((amdgpu_waves_per_eu(w1_waves(NI, EXP), w1_waves(NI, EXP)))) void 
     int64_t ldc, float* __restrict__ rowsum, int64_t m, int64_t row0, int sym,
     const float* __restrict__ colinv, int slice0, const float* __restrict__ gate, int gate_on,
     int ks_begin = 0, int ks_wrap = 0, int tcol0 = 0, int t_per = 0, int t_first = 0,
-    int t_nblk = 1, int64_t t_ostride = 0) {
+    int t_nblk = 1, int64_t t_ostride = 0, PW... pw_) {
+  static_assert(sizeof...(PW) == (FAM == kFamIMQ ? 1 : 0), "pw: the IMQ instantiations only");
+  [[maybe_unused]] const float pw = (0.f + ... + pw_);
   static_assert(NI == 4 || NI == 2, "NI: 4 or 2 column tiles per wave");
   static_assert(EXP || DS == 0, "the identity form is DS 0 only");
   const bool want_rs = EXP || rowsum != nullptr;   // (before the slice offset below)
@@ -159,7 +165,7 @@ __attribute__((amdgpu_waves_per_eu(w1_waves(NI, EXP), w1_waves(NI, EXP)))) void 
     C += (int64_t)(slice0 + bz) * m * ldc;
     rowsum += (int64_t)(slice0 + bz) * roundup128(m);
   }
-  const float scale = EXP ? -st->inv_h * kLog2e : 0.f;
+  const float scale = !EXP ? 0.f : FAM == kFamIMQ ? st->inv_h : -st->inv_h * kLog2e;
 
   // D: the block's panel row; thread t stages row t >> 1, columns 8 (t & 1) .. +7
   const __amdgpu_buffer_rsrc_t rD = __builtin_amdgcn_make_buffer_rsrc(
@@ -250,8 +256,9 @@ __attribute__((amdgpu_waves_per_eu(w1_waves(NI, EXP), w1_waves(NI, EXP)))) void 
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const float v = q < 4 ? d[0][q] : d[1][q - 4];
-        const float x = EXP ? __builtin_amdgcn_exp2f(fmaf(v, scale, F::kAScaleLog2))
-                            : v * F::kAScale;   // G 2^15 (exact)
+        const float x = !EXP ? v * F::kAScale   // G 2^15 (exact)
+                        : FAM == kFamIMQ ? imq_pow(v, scale, pw, F::kAScaleLog2)
+                                         : __builtin_amdgcn_exp2f(fmaf(v, scale, F::kAScaleLog2));
         e[q] = (EXP && !TR && qd == q) ? 0.f : x;
       }
       const float s = ((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7]));

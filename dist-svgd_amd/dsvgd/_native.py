@@ -27,11 +27,21 @@ class GramPart(ctypes.Structure):
                 ("kind", ctypes.c_int32), ("weight2", ctypes.c_int32)]
 
 
+class Kernel(ctypes.Structure):
+    """Mirror of dsvgd_kernel (include/dsvgd.h), passed by value."""
+    _fields_ = [("family", ctypes.c_int32), ("beta", ctypes.c_float)]
+
+
+KERNEL_RBF, KERNEL_IMQ = 0, 1
+
+
 class PhiPart(ctypes.Structure):
     """Mirror of dsvgd_phi_part (include/dsvgd.h)."""
     _fields_ = [("ky", _p), ("rs", _p), ("ldk", _i64), ("row_off", _i64), ("rows", _i64),
                 ("splits", _i64)]
 
+
+_k = Kernel
 
 # name -> (restype, argtypes); must mirror include/dsvgd.h exactly
 SIGNATURES = {
@@ -193,6 +203,26 @@ SIGNATURES = {
     "dsvgd_ksd_finish": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p,
                                 _int, _i64, _p, _p, _p, _p, _p]),
     "dsvgd_ksd_direct": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
+    # the entry points that take a kernel description (RBF or IMQ) by value
+    "dsvgd_phi_mm_kern": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p,
+                                 _k, _int, _p]),
+    "dsvgd_phi_mm_x3_kern": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p,
+                                    _int, _int, _p, _k, _int, _p]),
+    "dsvgd_phi_mm_h2_kern": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p,
+                                    _int, _p, _p, _k, _int, _p]),
+    "dsvgd_phi_finish_imq": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64,
+                                    _p, _k, _f, _f, _p, _i64, _p, _i64, _p, _i64, _p]),
+    "dsvgd_phi_direct_kern": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _f, _f, _p,
+                                     _i64, _p, _i64, _p, _i64, _p, _i64, _k, _p]),
+    "dsvgd_phi_row_kern": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _f, _p, _p, _k, _p]),
+    "dsvgd_phi_row_split_kern": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _f, _p, _p, _p,
+                                        _i64, _k, _p]),
+    "dsvgd_ksd_rows_kern": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _int,
+                                   _i64, _p, _p, _k, _p]),
+    "dsvgd_ksd_finish_imq": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64,
+                                    _i64, _p, _k, _int, _i64, _p, _p, _p, _p, _p]),
+    "dsvgd_ksd_direct_kern": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _k,
+                                     _p]),
 }
 
 

@@ -89,7 +89,7 @@ import torch
 from . import _native as N
 from . import exchange
 from .engine import PhiEngine, SelectState, StepGraph, sequential_sweep, span
-from .kernels import resolve_kernel
+from .kernels import IMQ, resolve_kernel
 from .targets import BuiltinTarget, LogisticRegression, resolve_target
 from .w2 import W2Term
 
@@ -141,6 +141,11 @@ class DistSampler(object):
             self._replicated = None if (N_local == N_global and
                                         hasattr(self._target, "fingerprint")) else False
         self._rbf = resolve_kernel(kernel, self._d)
+        if isinstance(self._rbf, IMQ):
+            # (the pair split, the blocked Gauss-Seidel sweeps and the
+            # one-operand phi are RBF forms)
+            raise ValueError("DistSampler: the distributed layouts are RBF-only for now; the "
+                             "inverse multiquadric kernel %r runs on dsvgd.Sampler" % (self._rbf,))
         # gathered-data all_scores: decided at the first step (needs the group)
         if gather_data not in (None, True, False):
             raise ValueError("gather_data must be None, True or False")

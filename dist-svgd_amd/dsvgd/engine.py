@@ -12,6 +12,10 @@ Per Jacobi step, all stream-ordered on the current HIP stream, no host sync:
   phi_mm                   [K Xc | K S], rowsum K, K = exp(-D/h) fused (MFMA)
   phi_finish               phi = (KS + 2/h (r x - K X)) / n ; X_own += step * phi
 
+With the inverse multiquadric kernel (kernel=IMQ) phi_mm runs twice, with
+F = u^beta and G' = u^(beta-1), u = 1 + D/h, fused the same way, and
+phi_finish_imq forms phi = (s + F S - (2 beta/h)(rG x - G' X)) / n.
+
 The hist all-reduce hook is where a DistSampler with a row-sharded D makes the
 median global (RCCL all_reduce of 2048 int64 counts per pass).
 """
@@ -23,8 +27,19 @@ import weakref
 import torch
 
 from . import _native as N
+from .kernels import IMQ, RBF
 
 NBINS = 2048
+
+
+def kernel_desc(kernel):
+    """The dsvgd_kernel (family, beta) of an RBF / IMQ / None, by value."""
+    if kernel is None or isinstance(kernel, RBF):
+        return N.Kernel(N.KERNEL_RBF, 0.0)
+    if isinstance(kernel, IMQ):
+        return N.Kernel(N.KERNEL_IMQ, kernel.beta)
+    raise ValueError("kernel must be a dsvgd.kernels.RBF, a dsvgd.kernels.IMQ or None "
+                     "(resolve a callable with dsvgd.kernels.resolve_kernel)")
 
 
 class _SelectState(ctypes.Structure):
@@ -181,7 +196,7 @@ class PhiEngine(object):
 
     def __init__(self, n, d, m=None, row0=0, device=None, local_median=False, gemm=None,
                  phi_gemm=None, gram_gemm=None, sym_layout=True, pair_split=None,
-                 phi_form=None):
+                 phi_form=None, kernel=None):
         """local_median: the median bandwidth is the lower median of the owned
         block's own m x n entries (k = (m n - 1) // 2, h = median / log n) --
         a rank-local bandwidth (the lagged DistSampler modes) -- instead of the
@@ -206,7 +221,17 @@ class PhiEngine(object):
         engages on the h2 engine with dp % 256 == 0, d > DIRECT_MAX_D, the
         fused scales and no pair split, else the engine keeps "xs"; the
         resolved form is `self.phi_form`, fixed for the engine's life.  A "w"
-        engine has no K . Xc, so ksd() raises on it."""
+        engine has no K . Xc, so ksd() raises on it.
+
+        kernel: an RBF (default), an IMQ or None -- only the family and beta
+        are read; the bandwidth still arrives through fixed_bandwidth /
+        median_bandwidth.  An IMQ engine runs the two-operand phi_mm twice
+        (phi_form "w" resolves to "xs") and refuses pair_split."""
+        self._kern = kernel_desc(kernel)
+        self.imq = self._kern.family == N.KERNEL_IMQ
+        if self.imq and pair_split is not None:
+            raise ValueError("pair_split is an RBF layout: the IMQ kernel runs on the row-block "
+                             "layout only")
         dev = N.require_gpu(device if device is not None else "cuda")
         lib = N.load()
         m = n if m is None else m
@@ -245,7 +270,7 @@ class PhiEngine(object):
             raise ValueError("phi_form must be 'xs' or 'w'")
         self.phi_form = "w" if (phi_form == "w" and phi_gemm == "h2" and self.dp % 256 == 0
                                 and d > self.DIRECT_MAX_D and self.fused_scales
-                                and pair_split is None) else "xs"
+                                and pair_split is None and not self.imq) else "xs"
         if phi_gemm == "x3":
             nb = lib.dsvgd_ysplit_bytes(self.n_pad, self.ldy)
             self.Yx = torch.empty(nb // 2, dtype=torch.int16, device=dev)
@@ -302,6 +327,10 @@ class PhiEngine(object):
             ky_slices = max(self.splits_fb, -(-self.splits * self.dp // self.ldy))
         self.KY = torch.empty(ky_slices * m, self.ldy, **f32)
         self.rowsum = torch.empty(max(self.splits, self.splits_fb) * self.m_pad, **f32)
+        if self.imq and d > self.DIRECT_MAX_D:
+            # the G' run's partials and row sums (KY / rowsum: the F run's)
+            self.KY2 = torch.empty_like(self.KY)
+            self.rowsum2 = torch.empty_like(self.rowsum)
         self.mean = torch.empty(d, **f32)    # the packing centre (dsvgd_colcenter)
         self.phi = torch.empty(m, d, **f32)
         self.state = SelectState(dev)
@@ -549,10 +578,19 @@ class PhiEngine(object):
         if self.d <= self.DIRECT_MAX_D:
             with span(self.timer, "phi_direct"):
                 # KY (the MFMA path's split-K buffer) doubles as the split-J scratch
+                if self.imq:
+                    N.call("dsvgd_phi_direct_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y),
+                           self.ldy, self.row0, self.m, self.n, self.d, self.state.ptr,
+                           float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx,
+                           N.ptr(self.KY), self.KY.numel(), self._kern, s)
+                    return
                 N.call("dsvgd_phi_direct", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
                        self.row0, self.m, self.n, self.d, self.state.ptr, float(inv_n),
                        float(step), ex, lde, phi, self.d, xo, ldx, N.ptr(self.KY),
                        self.KY.numel(), s)
+            return
+        if self.imq:
+            self._direction_imq(inv_n, step, ex, lde, phi, xo, ldx, s)
             return
         if self.phi_form == "w":
             self._direction_w(inv_n, step, ex, lde, phi, xo, ldx, s)
@@ -614,6 +652,80 @@ class PhiEngine(object):
         N.call("dsvgd_phi_finish", N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), self.splits,
                N.ptr(self.Y), self.ldy, self.row0, self.m, self.d, self.dp, self.state.ptr,
                float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx, s)
+
+    # ------------------------------------------------------------- IMQ --
+    def _imq_runs(self):
+        """(order, KY, rowsum, span name) of the two products: F = u^beta
+        into KY / rowsum, G' = u^(beta-1) into KY2 / rowsum2."""
+        return ((0, self.KY, self.rowsum, "phi_mm_f"), (1, self.KY2, self.rowsum2, "phi_mm_g"))
+
+    def _imq_fallback(self, gate, s):
+        """Both products again on the FmtH2 engine's fallback (the FmtX3
+        image and phi_mm_x3, or the exact f32 phi_mm where no FmtX3 image
+        fits), gated on the device word `gate`: nothing runs while it reads
+        0.  The range guard of direction() and the gate of ksd()."""
+        if self.Yx3 is None:
+            for order, KY, rs, _ in self._imq_runs():
+                N.call("dsvgd_phi_mm_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
+                       self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(KY),
+                       self.ldy, N.ptr(rs), gate, self._kern, order, s)
+            return
+        N.call("dsvgd_ysplit", N.ptr(self.Y), self.ldy, self.n_pad, N.ptr(self.Yx3),
+               0 if self.m16_fb else 1, gate, s)
+        for order, KY, rs, _ in self._imq_runs():
+            N.call("dsvgd_phi_mm_x3_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Yx3), self.ldy,
+                   self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(KY), self.ldy,
+                   N.ptr(rs), int(self.sym), int(self.m16_fb), gate, self._kern, order, s)
+
+    def _direction_imq(self, inv_n, step, ex, lde, phi, xo, ldx, s):
+        """phi with the IMQ kernel: the two-operand phi_mm twice on the
+        engine's MFMA path (each run its own KY / rowsum and, on FmtH2, its
+        own pass through the range guard's fallback), then phi_finish_imq.
+        F . Xc is computed and not used (DESIGN.md, "The IMQ kernel")."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        if self.sym and self.phi_gemm == "h2":
+            # (the slices follow the symmetric form in force, as direction())
+            want = int(N.load().dsvgd_phi_splits_sym(self.n, self.ldy))
+            if want != self.splits:
+                self.splits = want
+                self.KY = torch.empty(want * self.m, self.ldy, **f32)
+                self.rowsum = torch.empty(want * self.m_pad, **f32)
+                self.KY2, self.rowsum2 = torch.empty_like(self.KY), torch.empty_like(self.rowsum)
+        if self.phi_gemm == "h2":
+            guard = N.ptr(self.yscale) + 4 * (2 * self.ldy + 2)
+            with span(self.timer, "ysplit"):
+                self._scales(self.ldy, self.yscale, s)
+                N.call("dsvgd_h2_ysplit", N.ptr(self.Y), self.ldy, self.n_pad,
+                       N.ptr(self.yscale), N.ptr(self.Yx), s)
+            for order, KY, rs, name in self._imq_runs():
+                with span(self.timer, name):
+                    N.call("dsvgd_phi_mm_h2_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Yx),
+                           self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
+                           N.ptr(KY), self.ldy, N.ptr(rs), int(self.sym),
+                           N.ptr(self.yscale) + 4 * self.ldy, guard, self._kern, order, s)
+            with span(self.timer, "phi_guard"):
+                self._imq_fallback(guard, s)
+        elif self.x3:
+            m16 = self.m16
+            with span(self.timer, "ysplit"):
+                N.call("dsvgd_ysplit", N.ptr(self.Y), self.ldy, self.n_pad, N.ptr(self.Yx),
+                       0 if m16 else 1, None, s)
+            for order, KY, rs, name in self._imq_runs():
+                with span(self.timer, name):
+                    N.call("dsvgd_phi_mm_x3_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Yx),
+                           self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
+                           N.ptr(KY), self.ldy, N.ptr(rs), int(self.sym), int(m16), None,
+                           self._kern, order, s)
+        else:
+            for order, KY, rs, name in self._imq_runs():
+                with span(self.timer, name):
+                    N.call("dsvgd_phi_mm_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
+                           self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(KY),
+                           self.ldy, N.ptr(rs), None, self._kern, order, s)
+        N.call("dsvgd_phi_finish_imq", N.ptr(self.KY), self.ldy, N.ptr(self.KY2), self.ldy,
+               N.ptr(self.rowsum2), self.splits, N.ptr(self.Y), self.ldy, self.row0, self.m,
+               self.d, self.dp, self.state.ptr, self._kern, float(inv_n), float(step), ex, lde,
+               phi, self.d, xo, ldx, s)
 
     def _direction_w(self, inv_n, step, ex, lde, phi, xo, ldx, s):
         """phi_mm in the one-operand form: the scales and the image of W =
@@ -963,8 +1075,27 @@ class PhiEngine(object):
         W = self._ksd
         if direct:
             with span(self.timer, "ksd_direct"):
-                N.call("dsvgd_ksd_direct", N.ptr(self.Y), self.ldy, self.dp, self.d, self.row0,
-                       self.m, self.n, self.state.ptr, N.ptr(W["rows"]), N.ptr(W["ws"]),
+                N.call("dsvgd_ksd_direct_kern", N.ptr(self.Y), self.ldy, self.dp, self.d,
+                       self.row0, self.m, self.n, self.state.ptr, N.ptr(W["rows"]),
+                       N.ptr(W["ws"]), N.ptr(W["out"]), self._kern, s)
+        elif self.imq:
+            if self.phi_gemm == "h2":
+                # the gate reads the G' run's row sums rG (G' <= F entrywise);
+                # its fallback reruns both products
+                gate = N.ptr(W["gate"])
+                with span(self.timer, "ksd_gate"):
+                    N.call("dsvgd_ksd_gate", N.ptr(self.rowsum2), self.splits, self.m, self.n,
+                           gate, s)
+                    self._imq_fallback(gate, s)
+            with span(self.timer, "ksd_rows"):
+                N.call("dsvgd_ksd_rows_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
+                       self.dp, self.d, self.row0, self.m, self.n, self.state.ptr, sym,
+                       W["parts"], N.ptr(W["P"]), N.ptr(W["a"]), self._kern, s)
+            with span(self.timer, "ksd_finish"):
+                N.call("dsvgd_ksd_finish_imq", N.ptr(self.KY), self.ldy, N.ptr(self.KY2),
+                       self.ldy, N.ptr(self.rowsum2), self.splits, N.ptr(self.Y), self.ldy,
+                       self.dp, self.d, self.row0, self.m, self.n, self.state.ptr, self._kern,
+                       sym, W["parts"], N.ptr(W["P"]), N.ptr(W["rows"]), N.ptr(W["ws"]),
                        N.ptr(W["out"]), s)
         else:
             if self.phi_gemm == "h2":
@@ -1110,7 +1241,7 @@ def _gs_score_kind(target):
 
 
 def sequential_sweep(X, S, rows, h_state, step, target=None, score_scale=1.0, phi_out=None,
-                     extra=None, blocked=True, hold=None):
+                     extra=None, blocked=True, hold=None, kernel=None):
     """Gauss-Seidel sweep in the reference order over `rows` of the interacting
     set X (n, d): for each i, phi_i from the CURRENT X (earlier rows already
     moved), X[i] += step * (phi_i + extra[k]), then (if `target`) S[i] is
@@ -1129,7 +1260,14 @@ def sequential_sweep(X, S, rows, h_state, step, target=None, score_scale=1.0, ph
     hold: a dict the caller owns.  The wide sweep's workspace is stored in it,
     so it lives as long as the dict does: a caller that captures the sweep in
     a StepGraph keeps `hold` beside the graph, whose kernels hold raw pointers
-    into the workspace (the module's cache alone holds it weakly)."""
+    into the workspace (the module's cache alone holds it weakly).
+
+    kernel: an RBF (default), an IMQ or None (family and beta only; the
+    bandwidth is h_state's).  The blocked sweeps are RBF forms: an IMQ kernel
+    takes the per-row path whatever d is."""
+    kern = kernel_desc(kernel)
+    if kern.family == N.KERNEL_IMQ:
+        blocked = False
     n, d = X.shape
     s = N.stream(X.device)
     if extra is not None:
@@ -1159,11 +1297,11 @@ def sequential_sweep(X, S, rows, h_state, step, target=None, score_scale=1.0, ph
         ex = N.ptr(extra[k]) if extra is not None else None
         po = N.ptr(phi_out[k]) if phi_out is not None else None
         if part is None:
-            N.call("dsvgd_phi_row", N.ptr(X), N.ld(X), N.ptr(S), N.ld(S), n, d, int(i),
-                   h_state.ptr, float(step), ex, po, s)
+            N.call("dsvgd_phi_row_kern", N.ptr(X), N.ld(X), N.ptr(S), N.ld(S), n, d, int(i),
+                   h_state.ptr, float(step), ex, po, kern, s)
         else:
-            N.call("dsvgd_phi_row_split", N.ptr(X), N.ld(X), N.ptr(S), N.ld(S), n, d, int(i),
-                   h_state.ptr, float(step), ex, po, N.ptr(part), blocks, s)
+            N.call("dsvgd_phi_row_split_kern", N.ptr(X), N.ld(X), N.ptr(S), N.ld(S), n, d, int(i),
+                   h_state.ptr, float(step), ex, po, N.ptr(part), blocks, kern, s)
         if target is not None:
             target.score(X[i:i + 1], S[i:i + 1], score_scale)
 

@@ -29,7 +29,7 @@ def _device_f32(a, dev):
 
 def ksd(particles, logp, kernel=None, *, statistic="v", squared=False, device=None):
     """Kernelized Stein discrepancy (Liu, Lee and Jordan 2016; Chwialkowski et
-    al. 2016) between the particles and the target, for the RBF kernel: a
+    al. 2016) between the particles and the target, for the RBF or the IMQ kernel: a
     convergence measure that needs only the particles, their scores and the
     kernel -- the quantity the SVGD direction descends on.
 
@@ -66,7 +66,7 @@ def ksd(particles, logp, kernel=None, *, statistic="v", squared=False, device=No
     else:
         S = torch.empty(n, d, dtype=torch.float32, device=dev)
         resolve_target(logp).score(X, S)
-    eng = PhiEngine(n, d, device=dev)
+    eng = PhiEngine(n, d, device=dev, kernel=rbf)
     eng.pack(X, S)
     eng.distances(median=rbf.median)
     if rbf.median:

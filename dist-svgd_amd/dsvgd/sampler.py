@@ -17,8 +17,9 @@ Extensions (keyword-only, defaults keep the reference behaviour):
                       (built-in targets; default on);
   ksd_every           record the kernelized Stein discrepancy every k-th
                       timestep into `sampler.diagnostics` (default off).
-The kernel must be RBF-shaped (see dsvgd.kernels); RBF("median") selects the
-median-heuristic bandwidth h = median(D)/log(n), recomputed every iteration.
+The kernel must be RBF- or IMQ-shaped (see dsvgd.kernels); RBF("median") /
+IMQ("median") select the median-heuristic bandwidth h = median(D)/log(n),
+recomputed every iteration.
 """
 import numpy as np
 import pandas as pd
@@ -37,7 +38,7 @@ class Sampler(object):
 
         Params:
             d - dimensionality of each particle
-            kernel - kernel function (RBF family; see dsvgd.kernels)
+            kernel - kernel function (RBF or IMQ family; see dsvgd.kernels)
             logp - log density function, or a dsvgd.targets.Target
         """
         self._d = d
@@ -75,7 +76,7 @@ class Sampler(object):
         median = self._rbf.median
         # (ksd() reads K . Xc, which only the two-operand phi_mm leaves behind)
         form = "w" if ksd_every is None else "xs"
-        engine = (PhiEngine(n, d, device=dev, phi_form=form)
+        engine = (PhiEngine(n, d, device=dev, phi_form=form, kernel=self._rbf)
                   if (order == "jacobi" or median) else None)
         state = engine.state if engine is not None else SelectState(dev)
         if not median:
@@ -93,7 +94,8 @@ class Sampler(object):
                     engine.pack(X)
                     engine.distances(median=True)
                     engine.median_bandwidth()
-                sequential_sweep(X, S, range(n), state, step_size, target=target, hold=hold)
+                sequential_sweep(X, S, range(n), state, step_size, target=target, hold=hold,
+                                 kernel=self._rbf)
 
         # built-in targets are pure kernel launches: capture the iteration
         # once and replay it (user callables run eagerly)
@@ -107,7 +109,7 @@ class Sampler(object):
             kout = torch.empty(len(records), 4, dtype=torch.float64, device=dev)
             kh = torch.empty(len(records), dtype=torch.float32, device=dev)
             fused = order == "jacobi" and d > PhiEngine.DIRECT_MAX_D
-            keng = engine if fused else PhiEngine(n, d, device=dev)
+            keng = engine if fused else PhiEngine(n, d, device=dev, kernel=self._rbf)
             Sk = S if fused else torch.empty_like(S)
             h_fixed = None if median else self._rbf.h
 

@@ -924,6 +924,105 @@ int dsvgd_ksd_direct(const float* Y, int64_t ldy, int64_t dp, int64_t d, int64_t
                      int64_t n, const dsvgd_select_state* st, float* rows, double* ws, double* out,
                      void* stream);
 
+/* ---- a second radial kernel: the inverse multiquadric (IMQ) --------------
+ * The reference takes any kernel(x, y) callable and differentiates it by
+ * autograd per pair (dsvgd/sampler.py:7-40, dsvgd/distsampler.py:84-101).
+ * Beside k = exp(-|x - y|^2 / h) the engine has
+ *   k(x, y) = (1 + |x - y|^2 / h)^beta = u^beta,   -1 <= beta < 0,
+ * the kernel recommended for the KSD above a handful of dimensions (Gorham &
+ * Mackey 2017).  It is radial: the same D, the same bandwidth in `st`, the
+ * same engines.  Its gradient is not a multiple of itself, so it takes two
+ * kernel matrices: with F = u^beta, G' = u^(beta-1), c1 = -2 beta / h,
+ *   phi_i = inv_n [ s_i + (F S)_i + c1 (rG_i xc_i - (G' Xc)_i) ],
+ *   rG_i = sum_{j != i} G'_ij
+ * (the diagonal is skipped in both products; its term is s_i).  All powers of
+ * u lie in (0, 1] and the +inf pads of D map to 0, as exp(-D/h) does.
+ *
+ * A kernel is described on the host and passed BY VALUE to the entry points
+ * below, each beside the one it extends (no process-wide setting).  With the
+ * RBF family each one is the call beside it. */
+#define DSVGD_KERNEL_RBF 0 /* exp(-|x - y|^2 / h); beta is ignored          */
+#define DSVGD_KERNEL_IMQ 1 /* (1 + |x - y|^2 / h)^beta, beta in [-1, 0)     */
+typedef struct dsvgd_kernel {
+  int32_t family;
+  float beta;
+} dsvgd_kernel;
+
+/* dsvgd_phi_mm{,_gated,_x3,_h2} with the kernel `kern` fused into the A
+ * operand.  IMQ stages ONE power of u, u^e 2^15 = exp2(e log2(fma(D, 1/h, 1))
+ * + 15) (the FmtH2 A scale 2^15 as the RBF's; c1 is applied by the finish):
+ * order 0: e = beta (F), order 1: e = beta - 1 (G'; IMQ only) -- e is a launch
+ * argument, so both run the same code.  Same layouts, split-K slices,
+ * diagonal rule, range-guard gates and limits as the call each one extends
+ * (dsvgd_phi_mm_kern: gate == NULL is dsvgd_phi_mm, else dsvgd_phi_mm_gated).
+ * An IMQ direction is two calls (order 0 and 1) into two KY / rowsum pairs,
+ * then dsvgd_phi_finish_imq.  Replaces the kernel and its autograd gradient
+ * in dsvgd/sampler.py:26-40 for an IMQ callable. */
+int dsvgd_phi_mm_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                      int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
+                      float* KY, int64_t ldk, float* rowsum, const float* gate,
+                      dsvgd_kernel kern, int order, void* stream);
+int dsvgd_phi_mm_x3_kern(const float* D, int64_t ldd, const void* Yx, int64_t ldy, int64_t row0,
+                         int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
+                         float* KY, int64_t ldk, float* rowsum, int sym, int m16,
+                         const float* gate, dsvgd_kernel kern, int order, void* stream);
+int dsvgd_phi_mm_h2_kern(const float* D, int64_t ldd, const void* Yh, int64_t ldy, int64_t row0,
+                         int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
+                         float* KY, int64_t ldk, float* rowsum, int sym, const float* colinv,
+                         const float* gate, dsvgd_kernel kern, int order, void* stream);
+/* dsvgd_phi_finish for the IMQ kernel: KF = the order-0 run's [F Xc | F S]
+ * (only F S is read), KG = the order-1 run's [G' Xc | G' S] (only G' Xc) and
+ * its row sums `rowsum` = rG, `splits` slices each, summed in slice order;
+ * phi as above, extra / phi / X as dsvgd_phi_finish (the update of
+ * dsvgd/sampler.py:68 / dsvgd/distsampler.py:200, Jacobi order). */
+int dsvgd_phi_finish_imq(const float* KF, int64_t ldkf, const float* KG, int64_t ldkg,
+                         const float* rowsum, int64_t splits, const float* Y, int64_t ldy,
+                         int64_t row0, int64_t m, int64_t d, int64_t dp,
+                         const dsvgd_select_state* st, dsvgd_kernel kern, float inv_n, float step,
+                         const float* extra, int64_t lde, float* phi, int64_t ldphi, float* X,
+                         int64_t ldx, void* stream);
+/* dsvgd_phi_direct with a kernel: IMQ sums F_ij s_j + c1 G'_ij (x_i - x_j)
+ * per pair (dsvgd/sampler.py:38-40 with an IMQ kernel). */
+int dsvgd_phi_direct_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                          int64_t m, int64_t n, int64_t d, const dsvgd_select_state* st,
+                          float inv_n, float step, const float* extra, int64_t lde, float* phi,
+                          int64_t ldphi, float* X, int64_t ldx, float* partial,
+                          int64_t partial_floats, dsvgd_kernel kern, void* stream);
+/* dsvgd_phi_row / dsvgd_phi_row_split with a kernel (dsvgd/sampler.py:64-68
+ * with an IMQ kernel): IMQ keeps a second per-column coefficient, F_j on s_j
+ * and c1 G'_j on x_i - x_j (d <= 7808 for dsvgd_phi_row_kern; twice the rows'
+ * LDS for the split form). */
+int dsvgd_phi_row_kern(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n_int,
+                       int64_t d, int64_t i, const dsvgd_select_state* st, float step,
+                       const float* extra, float* phi_out, dsvgd_kernel kern, void* stream);
+int dsvgd_phi_row_split_kern(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n,
+                             int64_t d, int64_t i, const dsvgd_select_state* st, float step,
+                             const float* extra, float* phi_out, float* partial, int64_t blocks,
+                             dsvgd_kernel kern, void* stream);
+/* The KSD with a kernel (absent in the reference, as above).  For the IMQ,
+ * with H' = u^(beta-2) and c2 = 4 beta (beta - 1) / h^2,
+ *   u_ij = F s_i.s_j + c1 G' [(s_i - s_j).(x_i - x_j) + d] - c2 H' D_ij,
+ *   u_ii = |s_i|^2 + c1 d,
+ *   t_i = s_i.FS_i + c1 [rG_i a_i - s_i.G'Xc_i - xc_i.G'S_i + b_i + d rG_i]
+ *         - c2 q_i,   b_i = sum_{j != i} G'_ij a_j,  q_i = sum_{j != i} H'_ij D_ij.
+ * dsvgd_ksd_rows_kern: dsvgd_ksd_rows' sweep, slots and layouts with these b
+ * and q.  dsvgd_ksd_gate reads the G' run's row sums rG; its fallback reruns
+ * both products on the gate.  dsvgd_ksd_finish_imq: dsvgd_ksd_finish from the
+ * two runs' slices (KF: F S; KG: G' Xc and G' S; rowsum: rG).
+ * dsvgd_ksd_direct_kern: dsvgd_ksd_direct per pair.  Deterministic as above. */
+int dsvgd_ksd_rows_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t dp,
+                        int64_t d, int64_t row0, int64_t m, int64_t n,
+                        const dsvgd_select_state* st, int sym, int64_t parts, float* P, float* a,
+                        dsvgd_kernel kern, void* stream);
+int dsvgd_ksd_finish_imq(const float* KF, int64_t ldkf, const float* KG, int64_t ldkg,
+                         const float* rowsum, int64_t splits, const float* Y, int64_t ldy,
+                         int64_t dp, int64_t d, int64_t row0, int64_t m, int64_t n,
+                         const dsvgd_select_state* st, dsvgd_kernel kern, int sym, int64_t parts,
+                         const float* P, float* rows, double* ws, double* out, void* stream);
+int dsvgd_ksd_direct_kern(const float* Y, int64_t ldy, int64_t dp, int64_t d, int64_t row0,
+                          int64_t m, int64_t n, const dsvgd_select_state* st, float* rows,
+                          double* ws, double* out, dsvgd_kernel kern, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
