@@ -179,9 +179,13 @@ __attribute__((amdgpu_waves_per_eu(w1_waves(NI, EXP), w1_waves(NI, EXP)))) void 
   const int srow = t >> 1, shalf = t & 1;
   const int aoff = x3_off(srow, shalf);       // this thread's 16 B of a part image row
   // diagonal: global row - the thread's first column at K-step 0, clamped to
-  // int range (only |.| < 16 matters; DS 1 never meets it)
+  // int range (only |.| < 16 matters; DS 1 never meets it).  DS 0 cyclic
+  // window: K-steps are counted unwrapped from ks_begin, so a row left of the
+  // window's first column meets its own column ks_wrap K-steps later
   auto diag0 = [&](int kfirst) {
-    const int64_t dg = row0 + i0 + srow - 8 * shalf - (int64_t)kfirst * PhiW1::BJ;
+    int64_t dg = row0 + i0 + srow - 8 * shalf - (int64_t)kfirst * PhiW1::BJ;
+    if (DS == 0 && ks_wrap > 0 && row0 + i0 + srow < (int64_t)ks_begin * PhiW1::BJ)
+      dg += (int64_t)ks_wrap * PhiW1::BJ;
     return (int)max(min(dg, (int64_t)(1 << 30)), (int64_t)-(1 << 30));
   };
 

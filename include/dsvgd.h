@@ -493,9 +493,10 @@ int dsvgd_radix_hist_wmap(const float* D, int64_t m_pad, int64_t n_pad, const fl
 /* phi_mm (FmtH2) of rows [row0, row0 + m) of the interacting set (D: their
  * panel rows) over a CYCLIC window of columns [col0, col0 + wlen) mod
  * n_pad, into `splits` split-K slices (KY + z m ldk, rowsum + z
- * roundup(m,128)); the diagonal j == row0 + i skipped as in dsvgd_phi_mm.
- * col0, wlen multiples of 16.  gate / gate_on as dsvgd_phi_mm_h2 (run iff
- * (*gate != 0) == gate_on). */
+ * roundup(m,128)); the diagonal j == row0 + i skipped as in dsvgd_phi_mm
+ * wherever the window holds it, before or after the wrap (a row left of col0
+ * meets its own column in the wrapped part).  col0, wlen multiples of 16.
+ * gate / gate_on as dsvgd_phi_mm_h2 (run iff (*gate != 0) == gate_on). */
 int dsvgd_phi_h2_window(const float* D, int64_t ldd, const void* Yh, int64_t ldy, int64_t row0,
                         int64_t m, int64_t n, int64_t col0, int64_t wlen,
                         const dsvgd_select_state* st, int64_t splits, float* KY, int64_t ldk,
@@ -506,7 +507,10 @@ int dsvgd_phi_h2_window(const float* D, int64_t ldd, const void* Yh, int64_t ldy
  * yrow0 + krows - 1), its columns [col0, col0 + mo) (col0 a multiple of
  * 128).  P_z[i][:] = sum_{j in slice z} exp(-D[j][col0 + i]/h) Y[yrow0 + j][:]
  * and rs_z[i] the same sum of the weights, for i < mo (KY layout: P + z mo
- * ldp, rs + z roundup(mo,128)).  krows a multiple of 16. */
+ * ldp, rs + z roundup(mo,128)).  krows a multiple of 16.  No diagonal rule:
+ * a rectangle that holds entries j == col0 + i - yrow0 of D's diagonal sums
+ * their k_ii like any other weight (the layout's rectangles are off-diagonal
+ * blocks).  The same holds for the two batched forms below. */
 int dsvgd_phi_h2_transposed(const float* D, int64_t ldd, const void* Yh, int64_t ldy,
                             int64_t yrow0, int64_t krows, int64_t col0, int64_t mo, int64_t n,
                             const dsvgd_select_state* st, int64_t splits, float* P, int64_t ldp,
@@ -531,14 +535,19 @@ int dsvgd_phi_h2_transposed_blocks_split(const float* D, int64_t ldd, const void
                                          const dsvgd_select_state* st, float* P, int64_t ldp,
                                          int64_t pstride, const float* colinv, const float* gate,
                                          int gate_on, void* stream);
-/* For q < count: out + q ostride = sum over z < zsplit (in slice order) of
- * the [rows x ldp | row sums] partial at P + (z count + q) pstride (row sums
- * at + rows ldp in, + rows ldo out) -- the split forward blocks' messages. */
+/* For q < count: out + q ostride = sum over z < zsplit of the [rows x ldp |
+ * row sums] partial at P + (z count + q) pstride (row sums at + rows ldp in,
+ * + rows ldo out) -- the split forward blocks' messages.  The order of
+ * dsvgd_phi_partial_reduce. */
 int dsvgd_phi_partial_reduce_blocks(const float* P, int64_t ldp, int64_t pstride, int64_t zsplit,
                                     int64_t count, int64_t rows, int64_t cols, float* out,
                                     int64_t ldo, int64_t ostride, void* stream);
-/* out[i][c] = sum_z P[z][i][c] (c < cols) and out_rs[i] = sum_z rs[z][i], in
- * slice order (the P / rs layout of dsvgd_phi_h2_transposed). */
+/* out[i][c] = sum_z P[z][i][c] (c < cols) and out_rs[i] = sum_z rs[z][i] (the
+ * P / rs layout of dsvgd_phi_h2_transposed), in a fixed order: with G = the
+ * slice count rounded up to a power of two, at most 16, group g < G sums the
+ * slices g, g + G, g + 2 G, ... in that order from zero, and the G group sums
+ * are then added in g order -- slice order up to 16 slices, interleaved
+ * groups beyond. */
 int dsvgd_phi_partial_reduce(const float* P, int64_t ldp, const float* rs, int64_t splits,
                              int64_t rows, int64_t cols, float* out, int64_t ldo, float* out_rs,
                              void* stream);
