@@ -163,6 +163,10 @@ SIGNATURES = {
                                         _p]),
     "dsvgd_logreg_predict_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i64]),
     "dsvgd_logreg_predict": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p]),
+    # the Bayesian neural-network regression target (csrc/bnn.hip)
+    "dsvgd_score_bnn": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _f, _f, _f,
+                               _p, _i64, _p]),
+    "dsvgd_bnn_predict": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p]),
     # the wide blocked Gauss-Seidel sweep (ABI 4)
     "dsvgd_gsw_block_rows": (_i64, [_i64, _int]),
     "dsvgd_gsw_debug": (_int, [_int]),

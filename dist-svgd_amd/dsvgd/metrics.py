@@ -12,6 +12,11 @@ within ~1e-6 of 0.5 may land on the other side.
 `ksd` is the sampler's own convergence measure, for any target: the
 kernelized Stein discrepancy of a particle set (no counterpart in the
 reference; csrc/ksd.hip).
+
+`bnn_predict`, `bnn_rmse` and `bnn_loglik` evaluate the particles of the
+Bayesian neural-network regression target (dsvgd.targets.BayesianNN) on a
+test set: every particle's predictions in `dsvgd_bnn_predict` (csrc/bnn.hip),
+the two reductions over them in fp64 torch on the device.
 """
 import math
 
@@ -77,6 +82,45 @@ def ksd(particles, logp, kernel=None, *, statistic="v", squared=False, device=No
     out = eng.ksd().cpu()
     val = float(out[2] if statistic == "v" else out[3])
     return val if squared else math.sqrt(max(val, 0.0))
+
+
+def bnn_predict(particles, target_or_hidden, x_test):
+    """(n, Nt) device tensor F[i][q] = f_i(x_test_q): every particle's network
+    (dsvgd.targets.BayesianNN's layout) at the test rows, through
+    `dsvgd_bnn_predict`.  target_or_hidden: the BayesianNN target, or its
+    hidden width."""
+    hidden = getattr(target_or_hidden, "hidden", target_or_hidden)
+    X = torch.as_tensor(particles)
+    dev = N.require_gpu(X.device if X.is_cuda else "cuda")
+    X = _device_f32(X, dev)
+    n, d = X.shape
+    xt = _device_f32(x_test, dev)
+    if xt.dim() != 2 or d != hidden * (xt.shape[1] + 2) + 3:
+        raise ValueError("x_test must be (Nt, p) with d = hidden (p + 2) + 3 = %d" % d)
+    Nt, p = xt.shape
+    F = torch.empty(n, Nt, dtype=torch.float32, device=dev)
+    N.call("dsvgd_bnn_predict", N.ptr(X), N.ld(X), n, d, N.ptr(xt), N.ld(xt), Nt, p, int(hidden),
+           N.ptr(F), N.ld(F), N.stream(dev))
+    return F
+
+
+def bnn_rmse(particles, target, x_test, y_test):
+    """RMSE of the particle-mean prediction on the test set (a Python float)."""
+    F = bnn_predict(particles, target, x_test).double()
+    y = torch.as_tensor(y_test).to(device=F.device, dtype=torch.float64).reshape(-1)
+    return float(((F.mean(0) - y) ** 2).mean().sqrt())
+
+
+def bnn_loglik(particles, target, x_test, y_test):
+    """Mean test log-likelihood of the particle mixture,
+    mean_q log (1/n) sum_i N(y_q; F_iq, 1 / gamma_i), gamma_i = exp(x_i[d-2]);
+    reduced in fp64 on the device (a Python float)."""
+    F = bnn_predict(particles, target, x_test).double()
+    dev = F.device
+    y = torch.as_tensor(y_test).to(device=dev, dtype=torch.float64).reshape(-1)
+    lg = torch.as_tensor(particles)[:, -2].to(device=dev, dtype=torch.float64)
+    comp = 0.5 * (lg[:, None] - math.log(2.0 * math.pi)) - 0.5 * torch.exp(lg)[:, None] * (y - F) ** 2
+    return float((torch.logsumexp(comp, 0) - math.log(F.shape[0])).mean())
 
 
 def predictive_prob(particles, x_test):

@@ -7,7 +7,8 @@ particles in one batched device call:
 
 * built-in targets run hand-written gfx950 kernels (libdsvgd_hip.so):
   :class:`Gaussian`, :class:`GaussianMixture1D` (experiments/gmm.py:16-21),
-  :class:`LogisticRegression` (experiments/logreg.py:45-58, two MFMA GEMMs);
+  :class:`LogisticRegression` (experiments/logreg.py:45-58, two MFMA GEMMs),
+  :class:`BayesianNN` (beyond the reference: one kernel, csrc/bnn.hip);
 * any other `logp` callable is wrapped by :class:`CallableTarget`, which runs
   the user's own torch code under ``torch.func.vmap(torch.func.grad(logp))``
   on the particles' device (user code, not a dsvgd compute path).
@@ -217,6 +218,85 @@ class LogisticRegression(BuiltinTarget):
         self._ws.clear()
         self._prepared.clear()
         self._pinned.clear()
+
+
+class BayesianNN(BuiltinTarget):
+    """Bayesian neural-network regression (Liu & Wang 2016): one hidden ReLU
+    layer of `hidden` units, Gamma(a0, b0) hyper-priors on the noise precision
+    gamma and the weight precision lambda (carried as logs, with the
+    log-Jacobian).  Not in the reference, whose users would pass this logp.
+
+        x = [vec(W1) (p x H row-major) | b1 (H) | w2 (H) | b2 | log gamma | log lambda]
+        d = H (p + 2) + 3,   f(z) = w2 . relu(W1^T z + b1) + b2
+
+    The score is one kernel, a workgroup per particle (csrc/bnn.hip)."""
+
+    MAX_WIDTH = 64    # largest p and hidden (dsvgd_score_bnn)
+
+    def __init__(self, x_train, y_train, hidden=50, a0=1.0, b0=0.1):
+        self.x = torch.as_tensor(x_train, dtype=torch.float32)
+        self.y = torch.as_tensor(y_train, dtype=torch.float32).reshape(-1)
+        if self.x.dim() != 2 or self.x.shape[0] != self.y.shape[0] or self.x.shape[0] < 1:
+            raise ValueError("x_train must be (N, p) and y_train (N,), N >= 1")
+        self.hidden = int(hidden)
+        if not 1 <= self.hidden <= self.MAX_WIDTH:
+            raise ValueError("hidden must be in [1, %d], got %r" % (self.MAX_WIDTH, hidden))
+        if not 1 <= self.p <= self.MAX_WIDTH:
+            raise ValueError("x_train must have 1 to %d columns, got %d" % (self.MAX_WIDTH, self.p))
+        self.a0, self.b0 = float(a0), float(b0)
+        self._dev = {}
+
+    @property
+    def N(self):
+        return self.x.shape[0]
+
+    @property
+    def p(self):
+        return self.x.shape[1]
+
+    @property
+    def d(self):
+        return self.hidden * (self.p + 2) + 3
+
+    def unpack(self, x):
+        """(W1 (p, H), b1, w2, b2, log gamma, log lambda) views of a particle."""
+        p, H = self.p, self.hidden
+        return (x[:p * H].reshape(p, H), x[p * H:p * H + H], x[p * H + H:p * H + 2 * H],
+                x[p * H + 2 * H], x[-2], x[-1])
+
+    def logp(self, x):
+        if x.shape[-1] != self.d:
+            raise ValueError("BayesianNN target has d = H (p + 2) + 3 = %d" % self.d)
+        z, y = self.x.to(device=x.device, dtype=x.dtype), self.y.to(device=x.device, dtype=x.dtype)
+        W1, b1, w2, b2, lg, ll = self.unpack(x)
+        r = y - (torch.relu(z @ W1 + b1) @ w2 + b2)
+        theta = x[:-2]
+        return (0.5 * self.N * lg - 0.5 * torch.exp(lg) * (r * r).sum()
+                + 0.5 * (self.d - 2) * ll - 0.5 * torch.exp(ll) * (theta * theta).sum()
+                + self.a0 * lg - self.b0 * torch.exp(lg) + self.a0 * ll - self.b0 * torch.exp(ll))
+
+    def _params(self, dev):
+        if dev not in self._dev:
+            self._dev[dev] = (self.x.to(dev).contiguous(), self.y.to(dev).contiguous())
+        return self._dev[dev]
+
+    def fingerprint(self):
+        """Digest of the data and the model (hidden, a0, b0)."""
+        import hashlib
+        import struct
+        h = hashlib.sha1(b"bnn")
+        h.update(struct.pack("<qqqdd", self.N, self.p, self.hidden, self.a0, self.b0))
+        h.update(_host_bytes(self.x))
+        h.update(_host_bytes(self.y))
+        return h.hexdigest()
+
+    def score(self, X, out, scale=1.0):
+        n, d = X.shape
+        assert d == self.d, "BayesianNN target has d = H (p + 2) + 3 = %d" % self.d
+        z, y = self._params(X.device)
+        N.call("dsvgd_score_bnn", N.ptr(X), N.ld(X), n, d, N.ptr(z), N.ld(z), N.ptr(y), self.N,
+               self.p, self.hidden, self.a0, self.b0, float(scale), N.ptr(out), N.ld(out),
+               N.stream(X.device))
 
 
 class CallableTarget(Target):

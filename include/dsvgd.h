@@ -868,6 +868,30 @@ size_t dsvgd_logreg_predict_workspace_bytes(int64_t n, int64_t Nt, int64_t p);
 int dsvgd_logreg_predict(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Xt,
                          int64_t ldxt, int64_t Nt, float* prob, void* workspace, void* stream);
 
+/* Bayesian neural-network regression (Liu & Wang 2016: one hidden ReLU layer
+ * of H units, Gamma(a0, b0) hyper-priors on the noise precision g and the
+ * weight precision l, both carried as logs with the log-Jacobian):
+ *   x = [vec(W1) (p x H row-major) | b1 (H) | w2 (H) | b2 | log g | log l],
+ *   d = H (p + 2) + 3,  f(z) = w2 . relu(W1^T z + b1) + b2,  r_q = y_q - f(z_q),
+ *   log p = N/2 log g - g/2 sum_q r_q^2 + (d-2)/2 log l - l/2 |x[:d-2]|^2
+ *           + a0 log g - b0 g + a0 log l - b0 l.
+ * S = scale * grad log p (the whole gradient, prior included; relu'(0) = 0)
+ * for n particles over N data rows Z (N x p, ldz) with targets y, in exact
+ * fp32 FMAs on the VALU: one workgroup per particle, the data in chunks of
+ * 256 rows, every sum in a fixed order (the same bits on every call, and a
+ * particle's score does not depend on n).  1 <= p, H <= 64; any n, N >= 1.
+ * No workspace.  Absent in the reference: replaces a user logp of this model
+ * differentiated by autograd (dsvgd/sampler.py:28-33 _dlogp). */
+int dsvgd_score_bnn(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Z, int64_t ldz,
+                    const float* y, int64_t N, int64_t p, int64_t H, float a0, float b0,
+                    float scale, float* S, int64_t lds, void* stream);
+/* F[i][q] = f_i(zt_q): each particle's network at the Nt rows of Zt (F: n x
+ * Nt, ldf >= Nt); the same forward pass as dsvgd_score_bnn.  Absent in the
+ * reference: replaces evaluating the user's network per particle in torch. */
+int dsvgd_bnn_predict(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Zt,
+                      int64_t ldz, int64_t Nt, int64_t p, int64_t H, float* F, int64_t ldf,
+                      void* stream);
+
 /* ---- kernelized Stein discrepancy of a Jacobi step's particles ---------
  * (absent in the reference, whose only diagnostics are the test accuracy of
  * experiments/logreg_plots.py and the KDE plot of experiments/gmm_plots.py.)
