@@ -302,7 +302,7 @@ __global__ __launch_bounds__(512, 1) void logreg_z_x3p_kernel(
 // ---- the fused score (round 5): Z, sigma and G . Xd in one kernel ---------
 // Per block 128 particles (4 waves x 32); per wave the 32 particles' W image
 // fragments stay in registers (the B operand of Z^T = Xd W^T, 16 K-steps x
-// 2 parts at p <= 255) and their 32 x 256 G . Xd accumulators in AGPRs.  The
+// 2 parts at p <= 256) and their 32 x 256 G . Xd accumulators in AGPRs.  The
 // data go by in chunks of 32 rows, DMA'd to LDS one chunk ahead: the chunk's
 // row image (Z^T's A operand, shared by the 4 waves) and its 2 K-steps of
 // Xd's column image.  Z^T's C layout puts particle r in lane r & 31 and the
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256) void ysplit_h2_perm_kernel(const float* __rest
 
 constexpr int kFusedRows = 128;   // particles per block
 constexpr int kFusedChunk = 32;   // data rows per chunk
-constexpr int kFusedKD = 16;      // K-steps over the weights (p <= 255)
+constexpr int kFusedKD = 16;      // K-steps over the weights (224 < p <= 256)
 constexpr int kFusedCols = 256;   // G . Xd columns (ldb)
 constexpr int kFusedXdx = kFusedKD * 2 * kFusedChunk * 32;   // a chunk's row image (32 KiB)
 constexpr int kFusedXdp = 2 * 2 * kFusedCols * 32;           // its 2 K-steps of column image
@@ -734,6 +734,9 @@ int dsvgd_logreg_set_fused(int on) {
 size_t dsvgd_logreg_workspace_bytes(int64_t n, int64_t N, int64_t p) {
   return logreg_ws(n, N, p).total;
 }
+
+static bool logreg_small(int64_t n, int64_t N, int64_t p);
+int dsvgd_logreg_small(int64_t n, int64_t N, int64_t p) { return logreg_small(n, N, p) ? 1 : 0; }
 
 // engine: 0 = FmtH2 split engine (default), 1 = FmtX3, 2 = f32 MFMA (reference)
 // The data-only half of the workspace (padded Xd / t, Xd's scales and images)

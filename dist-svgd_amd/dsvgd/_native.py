@@ -152,6 +152,7 @@ SIGNATURES = {
     "dsvgd_score_gaussian": (_int, [_p, _i64, _i64, _i64, _p, _p, _f, _p, _i64, _p]),
     "dsvgd_score_gmm": (_int, [_p, _i64, _i64, _i64, _f, _p, _i64, _p]),
     "dsvgd_logreg_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i64]),
+    "dsvgd_logreg_small": (_int, [_i64, _i64, _i64]),
     "dsvgd_score_logreg": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _f, _p, _i64, _p,
                                   _p]),
     "dsvgd_score_logreg_engine": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _f, _p, _i64,

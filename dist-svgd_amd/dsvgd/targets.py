@@ -184,7 +184,7 @@ class LogisticRegression(BuiltinTarget):
         # (release() frees them explicitly); of the others the
         # MAX_WORKSPACES most recently used stay.  The few-particle path
         # (the Gauss-Seidel refreshes) needs none.
-        small = n <= self.SMALL_ROWS and (d - 1 <= 32 or self.N <= 8192)   # logreg.hip's test
+        small = bool(N.load().dsvgd_logreg_small(n, self.N, d - 1))   # logreg.hip's own test
         key = (X.device, 0 if small else n)
         ws = self._workspace(key, n, d, X.device)
         base = ws.data_ptr()

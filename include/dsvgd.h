@@ -827,6 +827,11 @@ int dsvgd_score_gmm(const float* X, int64_t ldx, int64_t n, int64_t d, float sca
  * setting.  The prepared workspace holds both paths' data images. */
 int dsvgd_logreg_set_fused(int on);
 size_t dsvgd_logreg_workspace_bytes(int64_t n, int64_t N, int64_t p);
+/* 1 where n particles, N data rows and p = d - 1 weights take the
+ * one-block-per-particle path, n <= 32 and (p <= 32 or N <= 8192): no
+ * workspace is read there, and dsvgd_logreg_prepare / _prepared / _prior
+ * refuse the shape.  0 otherwise.  Host only (no device call). */
+int dsvgd_logreg_small(int64_t n, int64_t N, int64_t p);
 int dsvgd_score_logreg(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Xd,
                        int64_t ldxd, const float* t, int64_t N, float scale, float* S, int64_t lds,
                        void* workspace, void* stream);
