@@ -118,13 +118,20 @@ __device__ __forceinline__ float bnn_forward_row(const float* W1s, const float* 
 
 // kPredict: out[i][q] = f_i(z_q) (y, a0, b0, scale unused); otherwise out[i] =
 // scale * grad log p(x_i).
-template <bool kPredict>
+// kWindow: the likelihood over the cyclic window of `cnt` rows that starts at
+// row *cursor, rows (c + q) mod N for q < cnt, its terms weighted wt = N / cnt
+// (the minibatch estimate); the prior terms count once.  Without it the
+// origin is 0, the count N and the weight 1, and none of the three is read:
+// the full-data kernels keep their code.
+template <bool kPredict, bool kWindow>
 __global__ __launch_bounds__(kBnnRows) void bnn_kernel(const float* __restrict__ X, int64_t ldx,
                                                        int d, const float* __restrict__ Z,
                                                        int64_t ldz, const float* __restrict__ y,
                                                        int64_t N, int p, int H, float a0, float b0,
                                                        float scale, float* __restrict__ out,
-                                                       int64_t ldo) {
+                                                       int64_t ldo,
+                                                       const int64_t* __restrict__ cursor,
+                                                       int64_t cnt, float wt) {
   extern __shared__ __align__(16) float bnn_smem[];
   const int tid = threadIdx.x;
   const float* x = X + (int64_t)blockIdx.x * ldx;
@@ -165,8 +172,16 @@ __global__ __launch_bounds__(kBnnRows) void bnn_kernel(const float* __restrict__
   for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   float acc_w2 = 0.f, acc_b1 = 0.f, sr = 0.f, srr = 0.f;
   const int sq0 = tid / p, sk0 = tid - sq0 * p, sdq = kBnnRows / p, sdk = kBnnRows - sdq * p;
+  // the rows walked and the window's origin, brought into [0, N) whatever
+  // the cursor holds
+  const int64_t M = kWindow ? cnt : N;
+  int64_t org = 0;
+  if (kWindow) {
+    org = *cursor % N;
+    if (org < 0) org += N;
+  }
 
-  for (int64_t c0 = 0; c0 < N; c0 += kBnnRows) {
+  for (int64_t c0 = 0; c0 < M; c0 += kBnnRows) {
     // stage: consecutive threads take consecutive elements of the chunk, p
     // each (element tid + 256 j), eight loads in flight before their stores
     for (int j0 = 0, q = sq0, k = sk0; j0 < p; j0 += 8) {
@@ -175,8 +190,13 @@ __global__ __launch_bounds__(kBnnRows) void bnn_kernel(const float* __restrict__
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const bool on = j0 + u < p;
-        const int64_t row = c0 + q;
-        v[u] = (on && row < N) ? Z[row * ldz + k] : 0.f;
+        int64_t row = c0 + q;
+        const bool in = on && row < M;
+        if (kWindow) {
+          row += org;
+          if (row >= N) row -= N;
+        }
+        v[u] = in ? Z[row * ldz + k] : 0.f;
         at[u] = on ? q * sz + k : -1;
         q += sdq;
         k += sdk;
@@ -191,13 +211,18 @@ __global__ __launch_bounds__(kBnnRows) void bnn_kernel(const float* __restrict__
     }
     __syncthreads();
     {  // P1
-      const int64_t row = c0 + tid;
+      int64_t row = c0 + tid;
+      const bool in = row < M;
+      if (kWindow) {
+        row += org;
+        if (row >= N) row -= N;
+      }
       const float f =
           bnn_forward_row<!kPredict>(W1s, b1s, w2s, zs + tid * sz, Gs + tid * Hp, KQ, Hp) + b2;
       if (kPredict) {
-        if (row < N) o[row] = f;
+        if (in) o[row] = f;
       } else {
-        const float r = row < N ? y[row] - f : 0.f;
+        const float r = in ? y[row] - f : 0.f;
         rs[tid] = r;
         sr += r;
         srr = fmaf(r, r, srr);
@@ -258,6 +283,10 @@ __global__ __launch_bounds__(kBnnRows) void bnn_kernel(const float* __restrict__
   srr = bnn_block_sum(srr, red);
   const float lg = x[d - 2], ll = x[d - 1];
   const float gam = expf(lg), lam = expf(ll);
+  // the likelihood's weight rides on gamma (gw) and on the count of the
+  // log gamma entry (hn = wt cnt / 2); the priors read gam and lam
+  const float gw = kWindow ? __fmul_rn(wt, gam) : gam;
+  const float hn = kWindow ? __fmul_rn(wt, 0.5f * (float)cnt) : 0.5f * (float)N;
 
   // the partial sums: tiles over Gs (SG T 16 <= 256 Hp floats), d w2 and d b1
   // over zs (8 Hp <= 256 sz floats)
@@ -276,25 +305,26 @@ __global__ __launch_bounds__(kBnnRows) void bnn_kernel(const float* __restrict__
     const int tile = (k >> 2) * HQ + (h >> 2), at = 4 * (k & 3) + (h & 3);
     float s = Gs[tile * 16 + at];
     for (int g = 1; g < SG; ++g) s += Gs[(g * T + tile) * 16 + at];
-    o[e] = scale * fmaf(gam, s, -lam * W1s[k * Hp + h]);
+    o[e] = scale * fmaf(gw, s, -lam * W1s[k * Hp + h]);
   }
   for (int h = tid; h < H; h += kBnnRows) {
     const float sw = (zs[h] + zs[Hp + h]) + (zs[2 * Hp + h] + zs[3 * Hp + h]);
     const float sb = (zs[4 * Hp + h] + zs[5 * Hp + h]) + (zs[6 * Hp + h] + zs[7 * Hp + h]);
-    o[pH + h] = scale * fmaf(gam, sb, -lam * b1s[h]);
-    o[pH + H + h] = scale * fmaf(gam, sw, -lam * w2s[h]);
+    o[pH + h] = scale * fmaf(gw, sb, -lam * b1s[h]);
+    o[pH + H + h] = scale * fmaf(gw, sw, -lam * w2s[h]);
   }
   if (tid == 0) {
-    o[pH + 2 * H] = scale * fmaf(gam, sr, -lam * b2);
-    o[d - 2] = scale * (0.5f * (float)N - 0.5f * gam * srr + a0 - b0 * gam);
+    o[pH + 2 * H] = scale * fmaf(gw, sr, -lam * b2);
+    o[d - 2] = scale * (hn - 0.5f * gw * srr + a0 - b0 * gam);
     o[d - 1] = scale * (0.5f * (float)(d - 2) - 0.5f * lam * th + a0 - b0 * lam);
   }
 }
 
-template <bool kPredict>
+template <bool kPredict, bool kWindow = false>
 static int bnn_launch(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Z,
                       int64_t ldz, const float* y, int64_t N, int64_t p, int64_t H, float a0,
-                      float b0, float scale, float* out, int64_t ldo, void* stream) {
+                      float b0, float scale, float* out, int64_t ldo, void* stream,
+                      const int64_t* cursor = nullptr, int64_t cnt = 0, float wt = 1.f) {
   const BnnLayout L = bnn_layout((int)p, (int)H);
   const size_t smem = sizeof(float) * (size_t)L.floats;
   // once per process, for the largest net (so that no launch inside a graph
@@ -304,16 +334,25 @@ static int bnn_launch(const float* X, int64_t ldx, int64_t n, int64_t d, const f
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail_arg("bnn: device");
   bool& reserved = reserved_on[dev];
   if (!reserved) {
-    const void* fn = reinterpret_cast<const void*>(&bnn_kernel<kPredict>);
+    const void* fn = reinterpret_cast<const void*>(&bnn_kernel<kPredict, kWindow>);
     const int most = (int)sizeof(float) * bnn_layout(kBnnMax, kBnnMax).floats;
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
       return fail_arg("bnn: cannot reserve the chunk's LDS");
     reserved = true;
   }
-  hipLaunchKernelGGL(bnn_kernel<kPredict>, dim3((unsigned)n), dim3(kBnnRows), smem,
+  hipLaunchKernelGGL((bnn_kernel<kPredict, kWindow>), dim3((unsigned)n), dim3(kBnnRows), smem,
                      (hipStream_t)stream, X, ldx, (int)d, Z, ldz, y, N, (int)p, (int)H, a0, b0,
-                     scale, out, ldo);
-  return check_launch(kPredict ? "bnn_predict" : "score_bnn");
+                     scale, out, ldo, cursor, cnt, wt);
+  return check_launch(kPredict ? "bnn_predict" : kWindow ? "score_bnn_window" : "score_bnn");
+}
+
+// c <- (c + B) mod N: one thread, so that the window moves inside a captured
+// iteration (the origin lives on the device)
+__global__ void bnn_window_advance_kernel(int64_t* cursor, int64_t B, int64_t N) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  int64_t c = *cursor % N;
+  if (c < 0) c += N;
+  *cursor = (c + B) % N;
 }
 
 }  // namespace dsvgd
@@ -331,6 +370,29 @@ int dsvgd_score_bnn(const float* X, int64_t ldx, int64_t n, int64_t d, const flo
   DSVGD_REQUIRE(d == H * (p + 2) + 3, "bnn: d must be H (p + 2) + 3");
   DSVGD_REQUIRE(n > 0 && n <= 0x7fffffff && N > 0 && ldx >= d && lds >= d && ldz >= p, "sizes");
   return bnn_launch<false>(X, ldx, n, d, Z, ldz, y, N, p, H, a0, b0, scale, S, lds, stream);
+}
+
+int dsvgd_score_bnn_window(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Z,
+                           int64_t ldz, const float* y, int64_t N, int64_t p, int64_t H, float a0,
+                           float b0, float scale, const int64_t* cursor, int64_t B, float* S,
+                           int64_t lds, void* stream) {
+  DSVGD_REQUIRE(X && Z && y && S && cursor, "null pointer");
+  DSVGD_REQUIRE(p >= 1 && p <= kBnnMax && H >= 1 && H <= kBnnMax,
+                "bnn: 1 <= p <= 64 and 1 <= H <= 64");
+  DSVGD_REQUIRE(d == H * (p + 2) + 3, "bnn: d must be H (p + 2) + 3");
+  DSVGD_REQUIRE(n > 0 && n <= 0x7fffffff && N > 0 && ldx >= d && lds >= d && ldz >= p, "sizes");
+  DSVGD_REQUIRE(B >= 1 && B <= N, "bnn: the window needs 1 <= B <= N");
+  const float wt = (float)((double)N / (double)B);
+  return bnn_launch<false, true>(X, ldx, n, d, Z, ldz, y, N, p, H, a0, b0, scale, S, lds, stream,
+                                 cursor, B, wt);
+}
+
+int dsvgd_window_advance(int64_t* cursor, int64_t B, int64_t N, void* stream) {
+  DSVGD_REQUIRE(cursor, "null pointer");
+  DSVGD_REQUIRE(N > 0 && B >= 1 && B <= N, "window: 1 <= B <= N");
+  hipLaunchKernelGGL(bnn_window_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, cursor,
+                     B, N);
+  return check_launch("window_advance");
 }
 
 int dsvgd_bnn_predict(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Zt,

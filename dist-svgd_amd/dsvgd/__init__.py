@@ -9,6 +9,8 @@ from .sampler import Sampler  # noqa: E402
 from .distsampler import DistSampler  # noqa: E402
 from . import kernels, metrics, targets  # noqa: E402
 from .kernels import IMQ, RBF  # noqa: E402
+from .adagrad import AdaGrad  # noqa: E402
 from .engine import PhiEngine  # noqa: E402
 
-__all__ = ["name", "Sampler", "DistSampler", "RBF", "IMQ", "PhiEngine", "kernels", "metrics", "targets"]
+__all__ = ["name", "Sampler", "DistSampler", "RBF", "IMQ", "AdaGrad", "PhiEngine", "kernels", "metrics",
+           "targets"]

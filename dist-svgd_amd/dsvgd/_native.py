@@ -168,6 +168,12 @@ SIGNATURES = {
     "dsvgd_score_bnn": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _f, _f, _f,
                                _p, _i64, _p]),
     "dsvgd_bnn_predict": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p]),
+    # the minibatch window of the BNN score and its device cursor
+    "dsvgd_score_bnn_window": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _f, _f,
+                                      _f, _p, _i64, _p, _i64, _p]),
+    "dsvgd_window_advance": (_int, [_p, _i64, _i64, _p]),
+    # the AdaGrad-conditioned update (csrc/adagrad.hip)
+    "dsvgd_adagrad_step": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _f, _f, _f, _p]),
     # the wide blocked Gauss-Seidel sweep (ABI 4)
     "dsvgd_gsw_block_rows": (_i64, [_i64, _int]),
     "dsvgd_gsw_debug": (_int, [_int]),

@@ -78,6 +78,20 @@ describe them and time them at :134-135 but ship no code):
 Both require exchange_particles=False, exchange_scores=False (nothing but
 the travelling block is communicated) and include_wasserstein=False.
 
+AdaGrad steps (keyword `adagrad`: None, True or a dsvgd.AdaGrad): the owned
+rows move by Liu & Wang's rule, x += step_size * p / (eps + sqrt(G)), p the
+whole direction (the h * W2 rows included) and G its per-entry moving average
+of p^2, kept beside the owned block for the sampler's life.  Allowed where
+the owned block never changes: order="jacobi" with num_shards == 1 or
+exchange_particles=True, and lagged=None.  In partitions and the lagged modes
+the blocks travel, and their history would have to travel with them: refused
+at construction, as is the sequential order (its sweeps move the rows inside
+the kernels).
+
+A target with minibatches (targets.BayesianNN(batch=...)) moves to its next
+window once per step, after the step's last score call; every rank windows
+its own data and the cursors advance in lockstep.
+
 Deviation: exchange_scores with num_shards == 1 uses the local scores (the
 reference reads an uninitialised buffer there).
 """
@@ -88,7 +102,8 @@ import torch
 
 from . import _native as N
 from . import exchange
-from .engine import PhiEngine, SelectState, StepGraph, sequential_sweep, span
+from .adagrad import resolve_adagrad
+from .engine import AdaGradState, PhiEngine, SelectState, StepGraph, sequential_sweep, span
 from .kernels import IMQ, resolve_kernel
 from .targets import BuiltinTarget, LogisticRegression, resolve_target
 from .w2 import W2Term
@@ -105,7 +120,7 @@ class DistSampler(object):
                  N_local, N_global,
                  exchange_particles=True, exchange_scores=True, include_wasserstein=True,
                  *, order="sequential", device=None, group=None, replicated=None,
-                 lagged=None, gather_data=None):
+                 lagged=None, gather_data=None, adagrad=None):
         """Initializes a distributed SVGD sampler (distsampler.py:9-51)."""
         assert not (exchange_scores and not exchange_particles), \
             "must exchange particles to also exchange scores"
@@ -117,6 +132,16 @@ class DistSampler(object):
             raise ValueError("lagged modes travel blocks round-robin: they need "
                              "exchange_particles=False, exchange_scores=False, "
                              "include_wasserstein=False")
+        rule = resolve_adagrad(adagrad)
+        if rule is not None:
+            if order != "jacobi":
+                raise ValueError("adagrad needs order='jacobi': the sequential sweeps move "
+                                 "their rows inside the sweep kernels, which take fixed steps")
+            if lagged or not (num_shards == 1 or exchange_particles):
+                raise ValueError("adagrad keeps a history per owned row: it needs an owned "
+                                 "block that never changes (num_shards == 1 or "
+                                 "exchange_particles=True, lagged=None); in the partitions and "
+                                 "lagged modes the blocks travel between the ranks")
         self._lagged = lagged
         self._rank = rank
         self._num_shards = num_shards
@@ -186,6 +211,9 @@ class DistSampler(object):
         self._w2 = None
         self._side = None        # score all-reduce stream (Jacobi, S > 1)
         self._sbuf = None
+        # the AdaGrad rule and the history of the owned rows (the sampler's life)
+        self._ada = None if rule is None else (
+            rule, AdaGradState(self._particles_per_shard, self._d, self._device))
         self._graph = None
         self._graph_key = None
         self._sweep_hold = {}    # the sequential sweep's workspace (_graph points into it)
@@ -432,16 +460,22 @@ class DistSampler(object):
         rows_eng.sample_share = eng.sample_share
         run(rows_eng, 0.0, True, move=False)   # the row-block phi; particles unmoved
         X0 = X_own.clone()
-        run(eng, step, True)              # the pair split's step
+        # (AdaGrad: the pair split computes its phi without moving either;
+        # the rule is applied once below, from the layout that wins)
+        run(eng, step, True, move=self._ada is None)    # the pair split's step
         ref = rows_eng.phi
         if self._check_corrupt:            # tests: a partial gone wrong on this rank
             eng.phi[0, 0] += 1e3 * float(ref.abs().max())
         err = ((eng.phi - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).double()
         err = float(exchange.all_reduce_max(err.reshape(1), self._group)[0])
         self.pair_split_check = err
-        if not err <= self.PAIR_SPLIT_CHECK_TOL:     # (a NaN fails too)
-            X_own.copy_(X0)
-            X_own.add_(ref, alpha=step)
+        won = err <= self.PAIR_SPLIT_CHECK_TOL       # (a NaN fails too)
+        if self._ada is not None:
+            (eng if won else rows_eng).adagrad_update(X_own, step, *self._ada)
+        if not won:
+            if self._ada is None:
+                X_own.copy_(X0)
+                X_own.add_(ref, alpha=step)
             self._routes_ok = False
             self._engines = {(eng.n, eng.m, False, False): rows_eng}
             warnings.warn("DistSampler: the pair-split layout's first step differs from the "
@@ -555,8 +589,11 @@ class DistSampler(object):
                 if e.plan is not None:
                     p2p = lambda sends, recvs: exchange.exchange_p2p_async(sends, recvs,
                                                                            self._group)
-                e.direction(X[us:ue] if move else None, step, write_phi=write_phi, extra=w2g,
-                            p2p=p2p)
+                if self._ada is not None and move:
+                    e.adagrad_direction(X[us:ue], step, *self._ada, extra=w2g, p2p=p2p)
+                else:
+                    e.direction(X[us:ue] if move else None, step, write_phi=write_phi,
+                                extra=w2g, p2p=p2p)
 
             if eng.plan is not None and self.pair_split_check is None:
                 self._check_pair_split(eng, run, X[us:ue], step_size)
@@ -578,7 +615,7 @@ class DistSampler(object):
             tgt = None if self._exchange_scores else self._target
             sequential_sweep(Xi, Si, range(us - lo, ue - lo), state, step_size, target=tgt,
                              score_scale=scale, extra=w2g, hold=self._sweep_hold)
-
+        self._target.next_batch()     # (after the step's last score call)
 
     def make_step(self, step_size, h=1.0):
         """Performs one step of SVGD (distsampler.py:172-205).

@@ -160,6 +160,19 @@ def span(timer, name):
     return _NULL if timer is None else timer(name)
 
 
+class AdaGradState(object):
+    """The AdaGrad history of m moved rows: G (m, d) on the device, -1 where
+    a row has not stepped yet (dsvgd_adagrad_step reads the sign: no counter,
+    so a captured iteration replays correctly)."""
+
+    def __init__(self, m, d, device):
+        self.G = torch.empty(m, d, dtype=torch.float32, device=device)
+        self.reset()
+
+    def reset(self):
+        self.G.fill_(-1.0)
+
+
 class PhiEngine(object):
     timer = None
     # median select: bracketed (sample -> [lo, hi] -> candidates) when the
@@ -653,6 +666,22 @@ class PhiEngine(object):
                N.ptr(self.Y), self.ldy, self.row0, self.m, self.d, self.dp, self.state.ptr,
                float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx, s)
 
+    def adagrad_direction(self, X_own, step, rule, state, inv_n=None, extra=None, p2p=None):
+        """The AdaGrad-conditioned step (dsvgd.adagrad) of the owned rows:
+        direction() writes p = phi (+ extra) without moving anything, on
+        whichever path the engine takes, then one elementwise kernel updates
+        the history state.G and X_own in place.  No finish kernel differs."""
+        assert X_own.shape == (self.m, self.d) and state.G.shape == (self.m, self.d)
+        self.direction(None, 0.0, write_phi=True, inv_n=inv_n, extra=extra, p2p=p2p)
+        self.adagrad_update(X_own, step, rule, state)
+
+    def adagrad_update(self, X_own, step, rule, state):
+        """X_own and state.G moved by the rule from the direction in self.phi."""
+        with span(self.timer, "adagrad"):
+            N.call("dsvgd_adagrad_step", N.ptr(X_own), N.ld(X_own), N.ptr(self.phi),
+                   N.ld(self.phi), N.ptr(state.G), N.ld(state.G), self.m, self.d, float(step),
+                   float(rule.alpha), float(rule.eps), N.stream(self.device))
+
     # ------------------------------------------------------------- IMQ --
     def _imq_runs(self):
         """(order, KY, rowsum, span name) of the two products: F = u^beta
@@ -1136,8 +1165,9 @@ class PhiEngine(object):
 
     # ------------------------------------------------------------ helpers --
     def step(self, X, S, X_own=None, step=0.0, h=None, score_scale=1.0, allreduce=None,
-             write_phi=True, extra=None):
-        """One Jacobi step: h=None -> median bandwidth, else fixed h."""
+             write_phi=True, extra=None, adagrad=None):
+        """One Jacobi step: h=None -> median bandwidth, else fixed h.
+        adagrad=(rule, state): X_own moves by the AdaGrad rule instead."""
         self.pack(X, S, score_scale)
         median = h is None
         self.distances(median=median)
@@ -1145,6 +1175,9 @@ class PhiEngine(object):
             self.median_bandwidth(allreduce)
         else:
             self.fixed_bandwidth(h)
+        if adagrad is not None:
+            self.adagrad_direction(X_own, step, *adagrad, extra=extra)
+            return
         self.direction(X_own, step, write_phi, extra=extra)
 
     def dense_D(self, padded=False):

@@ -40,7 +40,8 @@ def ksd(particles, logp, kernel=None, *, statistic="v", squared=False, device=No
 
     particles: (n, d) tensor or array; logp: anything a Sampler takes, or an
     (n, d) tensor / array of precomputed scores grad log p(x_i); kernel:
-    anything a Sampler takes (default RBF("median")).  statistic "v": the
+    anything a Sampler takes (default RBF("median")).  A target with
+    minibatches is scored on all of its data (its `full` twin).  statistic "v": the
     V-statistic (1/n^2) sum_ij u_ij (>= 0 up to rounding); "u": the unbiased
     U-statistic over i != j (may be negative; NaN for n = 1).  Returns a Python
     float: sqrt(max(., 0)), or the statistic itself with squared=True.
@@ -70,7 +71,8 @@ def ksd(particles, logp, kernel=None, *, statistic="v", squared=False, device=No
         S = _device_f32(scores, dev)
     else:
         S = torch.empty(n, d, dtype=torch.float32, device=dev)
-        resolve_target(logp).score(X, S)
+        target = resolve_target(logp)
+        getattr(target, "full", target).score(X, S)
     eng = PhiEngine(n, d, device=dev, kernel=rbf)
     eng.pack(X, S)
     eng.distances(median=rbf.median)

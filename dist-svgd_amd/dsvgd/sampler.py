@@ -16,7 +16,11 @@ Extensions (keyword-only, defaults keep the reference behaviour):
   graphs              capture one iteration as a HIP graph and replay it
                       (built-in targets; default on);
   ksd_every           record the kernelized Stein discrepancy every k-th
-                      timestep into `sampler.diagnostics` (default off).
+                      timestep into `sampler.diagnostics` (default off);
+  adagrad             None (fixed steps), True or a dsvgd.AdaGrad: Liu &
+                      Wang's AdaGrad-conditioned steps (order="jacobi").
+A target with minibatches (targets.BayesianNN(batch=...)) is scored on window
+t of its data at iteration t, in both orders.
 The kernel must be RBF- or IMQ-shaped (see dsvgd.kernels); RBF("median") /
 IMQ("median") select the median-heuristic bandwidth h = median(D)/log(n),
 recomputed every iteration.
@@ -27,7 +31,8 @@ import torch
 from torch.distributions.normal import Normal
 
 from . import _native as N
-from .engine import PhiEngine, SelectState, StepGraph, sequential_sweep
+from .adagrad import resolve_adagrad
+from .engine import AdaGradState, PhiEngine, SelectState, StepGraph, sequential_sweep
 from .kernels import resolve_kernel
 from .targets import BuiltinTarget, resolve_target
 
@@ -49,8 +54,13 @@ class Sampler(object):
         self.diagnostics = None   # sample(ksd_every=k) leaves its KSD records here
 
     def sample(self, n, num_iter, step_size, *, order="sequential", device=None, verbose=True,
-               graphs=True, ksd_every=None):
+               graphs=True, ksd_every=None, adagrad=None):
         """Generate samples using SVGD (sampler.py:42-74).
+
+        adagrad=True or a dsvgd.AdaGrad moves the particles by the AdaGrad
+        rule, x += step_size * p / (eps + sqrt(G)), with G the moving average
+        of p^2 per entry, started afresh by every call (order="jacobi" only:
+        the sequential sweeps move their rows inside the kernels).
 
         ksd_every=k records the kernelized Stein discrepancy of the particles
         at timesteps 0, k, 2k, .. <= num_iter, with the bandwidth the sampler
@@ -63,6 +73,10 @@ class Sampler(object):
             if isinstance(ksd_every, bool) or int(ksd_every) != ksd_every or ksd_every <= 0:
                 raise ValueError("ksd_every must be a positive integer (or None)")
             ksd_every = int(ksd_every)
+        rule = resolve_adagrad(adagrad)
+        if rule is not None and order != "jacobi":
+            raise ValueError("adagrad needs order='jacobi': the sequential sweeps move their "
+                             "rows inside the sweep kernels, which take fixed steps")
         self.diagnostics = None
         dev = N.require_gpu(device if device is not None else "cuda")
         q = Normal(0, 1)
@@ -83,12 +97,20 @@ class Sampler(object):
             N.call("dsvgd_set_bandwidth", state.ptr, float(self._rbf.h), N.stream(dev))
         target = self._target
         hold = {}    # the sweep's workspace, alive while `step` replays through it
+        # the AdaGrad history starts afresh with every run, and so does a
+        # minibatch target's window: two runs from the same seed agree
+        ada = (rule, AdaGradState(n, d, dev)) if rule is not None else None
+        target.reset_batch()
 
         def iteration():
             target.score(X, S)
             if order == "jacobi":
-                engine.step(X, S, X_own=X, step=step_size, h=None if median else self._rbf.h,
-                            write_phi=False)
+                if ada is not None:
+                    engine.step(X, S, X_own=X, step=step_size,
+                                h=None if median else self._rbf.h, adagrad=ada)
+                else:
+                    engine.step(X, S, X_own=X, step=step_size,
+                                h=None if median else self._rbf.h, write_phi=False)
             else:
                 if median:
                     engine.pack(X)
@@ -96,6 +118,7 @@ class Sampler(object):
                     engine.median_bandwidth()
                 sequential_sweep(X, S, range(n), state, step_size, target=target, hold=hold,
                                  kernel=self._rbf)
+            target.next_batch()     # (after the iteration's last score call)
 
         # built-in targets are pure kernel launches: capture the iteration
         # once and replay it (user callables run eagerly)

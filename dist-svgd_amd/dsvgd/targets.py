@@ -34,6 +34,13 @@ class Target(object):
         """out[:] = scale * grad log p(X) for X (n, d) on the device."""
         raise NotImplementedError
 
+    def next_batch(self):
+        """Move to the next minibatch of the data (the samplers call this once
+        per iteration, after its last score call).  Full-data targets: nothing."""
+
+    def reset_batch(self, t=0):
+        """Set the minibatch of iteration t.  Full-data targets: nothing."""
+
     def __call__(self, x):
         return self.logp(x)
 
@@ -229,11 +236,19 @@ class BayesianNN(BuiltinTarget):
         x = [vec(W1) (p x H row-major) | b1 (H) | w2 (H) | b2 | log gamma | log lambda]
         d = H (p + 2) + 3,   f(z) = w2 . relu(W1^T z + b1) + b2
 
-    The score is one kernel, a workgroup per particle (csrc/bnn.hip)."""
+    The score is one kernel, a workgroup per particle (csrc/bnn.hip).
+
+    batch=B with 1 <= B < N scores a minibatch (Liu & Wang's estimate): the
+    likelihood over the cyclic window of B rows that starts at a cursor kept
+    on the device, weighted N / B, the priors once.  next_batch() moves the
+    window by B rows (a kernel: it replays inside a captured iteration),
+    reset_batch(t) puts it where iteration t finds it, (t B) mod N.  `logp`
+    stays the full-data density and `full` is the full-data twin (evaluation,
+    dsvgd.metrics.ksd).  batch=None or batch >= N is the full-data target."""
 
     MAX_WIDTH = 64    # largest p and hidden (dsvgd_score_bnn)
 
-    def __init__(self, x_train, y_train, hidden=50, a0=1.0, b0=0.1):
+    def __init__(self, x_train, y_train, hidden=50, a0=1.0, b0=0.1, batch=None):
         self.x = torch.as_tensor(x_train, dtype=torch.float32)
         self.y = torch.as_tensor(y_train, dtype=torch.float32).reshape(-1)
         if self.x.dim() != 2 or self.x.shape[0] != self.y.shape[0] or self.x.shape[0] < 1:
@@ -244,7 +259,16 @@ class BayesianNN(BuiltinTarget):
         if not 1 <= self.p <= self.MAX_WIDTH:
             raise ValueError("x_train must have 1 to %d columns, got %d" % (self.MAX_WIDTH, self.p))
         self.a0, self.b0 = float(a0), float(b0)
+        if batch is not None:
+            if isinstance(batch, bool) or int(batch) != batch or batch < 1:
+                raise ValueError("batch must be a positive integer (or None), got %r" % (batch,))
+            batch = int(batch) if batch < self.N else None    # the whole data: no window
+        self.batch = batch
         self._dev = {}
+        self._cursor = {}     # device -> int64[1], the window's first row
+        self._origin = 0      # where a cursor made from now on starts
+        self._last = None     # the device of the last score call
+        self._full = None
 
     @property
     def N(self):
@@ -253,6 +277,46 @@ class BayesianNN(BuiltinTarget):
     @property
     def p(self):
         return self.x.shape[1]
+
+    @property
+    def full(self):
+        """The full-data target over the same tensors (itself without a batch)."""
+        if self.batch is None:
+            return self
+        if self._full is None:
+            twin = BayesianNN.__new__(BayesianNN)
+            twin.__dict__.update(self.__dict__)
+            twin.batch, twin._cursor, twin._full = None, {}, None
+            self._full = twin
+        return self._full
+
+    def _window(self, dev):
+        """The cursor of `dev` (made on first use, outside any capture: the
+        samplers' first iteration runs eagerly)."""
+        cur = self._cursor.get(dev)
+        if cur is None:
+            cur = self._cursor[dev] = torch.full((1,), self._origin, dtype=torch.int64, device=dev)
+        self._last = dev
+        return cur
+
+    def next_batch(self):
+        """The window of the device in use (the last one scored on) moves by
+        `batch` rows, on that device's current stream."""
+        if self.batch is None:
+            return
+        if self._last is None:     # no device yet: the first cursor starts a window on
+            self._origin = (self._origin + self.batch) % self.N
+            return
+        N.call("dsvgd_window_advance", N.ptr(self._cursor[self._last]), self.batch, self.N,
+               N.stream(self._last))
+
+    def reset_batch(self, t=0):
+        """Every cursor (and any made later) to iteration t's window, (t batch) mod N."""
+        if self.batch is None:
+            return
+        self._origin = (int(t) * self.batch) % self.N
+        for cur in self._cursor.values():
+            cur.fill_(self._origin)
 
     @property
     def d(self):
@@ -281,11 +345,14 @@ class BayesianNN(BuiltinTarget):
         return self._dev[dev]
 
     def fingerprint(self):
-        """Digest of the data and the model (hidden, a0, b0)."""
+        """Digest of the data and the model (hidden, a0, b0, and the batch of
+        a minibatch target)."""
         import hashlib
         import struct
         h = hashlib.sha1(b"bnn")
         h.update(struct.pack("<qqqdd", self.N, self.p, self.hidden, self.a0, self.b0))
+        if self.batch is not None:
+            h.update(struct.pack("<q", self.batch))
         h.update(_host_bytes(self.x))
         h.update(_host_bytes(self.y))
         return h.hexdigest()
@@ -294,6 +361,12 @@ class BayesianNN(BuiltinTarget):
         n, d = X.shape
         assert d == self.d, "BayesianNN target has d = H (p + 2) + 3 = %d" % self.d
         z, y = self._params(X.device)
+        if self.batch is not None:
+            N.call("dsvgd_score_bnn_window", N.ptr(X), N.ld(X), n, d, N.ptr(z), N.ld(z), N.ptr(y),
+                   self.N, self.p, self.hidden, self.a0, self.b0, float(scale),
+                   N.ptr(self._window(X.device)), self.batch, N.ptr(out), N.ld(out),
+                   N.stream(X.device))
+            return
         N.call("dsvgd_score_bnn", N.ptr(X), N.ld(X), n, d, N.ptr(z), N.ld(z), N.ptr(y), self.N,
                self.p, self.hidden, self.a0, self.b0, float(scale), N.ptr(out), N.ld(out),
                N.stream(X.device))

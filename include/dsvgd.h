@@ -890,12 +890,46 @@ int dsvgd_logreg_predict(const float* X, int64_t ldx, int64_t n, int64_t d, cons
 int dsvgd_score_bnn(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Z, int64_t ldz,
                     const float* y, int64_t N, int64_t p, int64_t H, float a0, float b0,
                     float scale, float* S, int64_t lds, void* stream);
+/* The minibatch estimate of the same score (Liu & Wang's): the likelihood
+ * over the cyclic window of B rows that starts at row c = *cursor, rows
+ * (c + q) mod N for q < B, its terms weighted N / B -- the N/2 of the log g
+ * entry included, which becomes (N/B) B/2 -- and the prior terms once; scale
+ * applies to the sum.  cursor: one int64 in device memory, read by every
+ * workgroup (any value: taken mod N), so that a captured iteration replays
+ * with a moving window.  1 <= B <= N.  The same kernel as dsvgd_score_bnn
+ * with a row origin, a row count and a likelihood weight; dsvgd_score_bnn
+ * keeps its own instantiation and its bits. */
+int dsvgd_score_bnn_window(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Z,
+                           int64_t ldz, const float* y, int64_t N, int64_t p, int64_t H, float a0,
+                           float b0, float scale, const int64_t* cursor, int64_t B, float* S,
+                           int64_t lds, void* stream);
+/* *cursor <- (*cursor + B) mod N on the device (one thread, ordinary loads
+ * and stores), stream-ordered like every other entry point. */
+int dsvgd_window_advance(int64_t* cursor, int64_t B, int64_t N, void* stream);
 /* F[i][q] = f_i(zt_q): each particle's network at the Nt rows of Zt (F: n x
  * Nt, ldf >= Nt); the same forward pass as dsvgd_score_bnn.  Absent in the
  * reference: replaces evaluating the user's network per particle in torch. */
 int dsvgd_bnn_predict(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Zt,
                       int64_t ldz, int64_t Nt, int64_t p, int64_t H, float* F, int64_t ldf,
                       void* stream);
+
+/* ---- AdaGrad-conditioned update of the Jacobi order (csrc/adagrad.hip) ----
+ * Liu & Wang's rule, per entry of the m moved rows; p = phi (m x d, ldphi) is
+ * the whole direction, the h * W2 rows included:
+ *   G' = p^2                        where G < 0 (no history: the state starts
+ *                                   filled with -1, and the rule never
+ *                                   produces a negative entry),
+ *   G' = alpha G + (1 - alpha) p^2  elsewhere,
+ *   x += step p / (eps + sqrt(G')).
+ * X (ldx >= d) and G (ldg >= d) are updated in place.  No iteration counter:
+ * a step depends on its inputs alone, so a captured iteration replays
+ * correctly.  IEEE sqrt and division (eight roundings from p to x); 16-byte
+ * accesses where d, the leading dimensions and the pointers allow them.
+ * 0 <= alpha < 1, eps > 0.  Absent in the reference, which takes fixed
+ * steps (dsvgd/sampler.py:68). */
+int dsvgd_adagrad_step(float* X, int64_t ldx, const float* phi, int64_t ldphi, float* G,
+                       int64_t ldg, int64_t m, int64_t d, float step, float alpha, float eps,
+                       void* stream);
 
 /* ---- kernelized Stein discrepancy of a Jacobi step's particles ---------
  * (absent in the reference, whose only diagnostics are the test accuracy of
