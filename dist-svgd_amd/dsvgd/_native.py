@@ -162,6 +162,10 @@ SIGNATURES = {
                                            _p]),
     "dsvgd_score_logreg_prior": (_int, [_p, _i64, _i64, _i64, _i64, _f, _f, _p, _i64, _p, _int,
                                         _p]),
+    # the minibatch window of the logistic-regression score (csrc/logreg_window.hip)
+    "dsvgd_logreg_window_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i64]),
+    "dsvgd_score_logreg_window": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _f, _p, _i64,
+                                         _p, _int, _p, _i64, _p]),
     "dsvgd_logreg_predict_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i64]),
     "dsvgd_logreg_predict": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p]),
     # the Bayesian neural-network regression target (csrc/bnn.hip)

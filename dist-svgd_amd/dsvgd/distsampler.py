@@ -88,9 +88,13 @@ the blocks travel, and their history would have to travel with them: refused
 at construction, as is the sequential order (its sweeps move the rows inside
 the kernels).
 
-A target with minibatches (targets.BayesianNN(batch=...)) moves to its next
-window once per step, after the step's last score call; every rank windows
-its own data and the cursors advance in lockstep.
+A target with minibatches (targets.BayesianNN(batch=...) or
+targets.LogisticRegression(batch=...)) moves to its next window once per
+step, after the step's last score call; every rank windows its own data (its
+shard) and the cursors advance in lockstep.  The gathered-data mode pools the
+ranks' data, and a window over the pool is not the sum of the ranks' windows:
+gather_data=None resolves to off as soon as any rank's target has a batch,
+and gather_data=True with such a target raises ValueError.
 
 Deviation: exchange_scores with num_shards == 1 uses the local scores (the
 reference reads an uninitialised buffer there).
@@ -174,6 +178,10 @@ class DistSampler(object):
         # gathered-data all_scores: decided at the first step (needs the group)
         if gather_data not in (None, True, False):
             raise ValueError("gather_data must be None, True or False")
+        if gather_data and getattr(self._target, "batch", None) is not None:
+            raise ValueError("gather_data=True needs full-data targets: a window over the "
+                             "gathered data is not the sum of the ranks' windows (batch=%d)"
+                             % self._target.batch)
         self._gdata = False if (gather_data is False or not exchange_scores
                                 or num_shards == 1) else gather_data
         if gather_data and not (exchange_scores and num_shards > 1):
@@ -348,11 +356,14 @@ class DistSampler(object):
         """gather_data=None/True, first step: every rank's (x, t) gathered
         once when every rank's target is a LogisticRegression (one
         all_gather_object; all ranks decide alike from the same gathered
-        list); the gathered target scores the own block, prior weighted S."""
+        list); the gathered target scores the own block, prior weighted S.
+        A rank whose target has a batch reports itself unfit, so one such
+        rank turns the mode off for all."""
         import torch.distributed as dist
         m = self._particles_per_shard
         tg = self._target
-        ok = (type(tg) is LogisticRegression and m > LogisticRegression.SMALL_ROWS
+        ok = (type(tg) is LogisticRegression and tg.batch is None
+              and m > LogisticRegression.SMALL_ROWS
               and not self._lagged and self._exchange_particles)
         mine = (bool(ok), tg.x.cpu() if ok else None, tg.t.cpu() if ok else None,
                 tg.gemm if ok else None)
@@ -366,8 +377,9 @@ class DistSampler(object):
             every = (x.numel() + t.numel()) * 4 <= self.GATHER_DATA_MAX_BYTES
         if not every:
             if self._gdata:
-                raise ValueError("gather_data=True: every rank needs a LogisticRegression "
-                                 "target (same engine), more than %d particles per rank and "
+                raise ValueError("gather_data=True: every rank needs a full-data "
+                                 "LogisticRegression target (same engine, no batch), more "
+                                 "than %d particles per rank and "
                                  "at most GATHER_DATA_MAX_BYTES of data in all"
                                  % LogisticRegression.SMALL_ROWS)
             self._gdata = False

@@ -1260,7 +1260,10 @@ GS_BLOCK_MIN_ROWS = 128   # shorter sweeps keep the per-row kernels
 def _gs_score_kind(target):
     """The blocked sweeps refresh the built-in targets' scores themselves:
     dsvgd_gs_block_sweep's / dsvgd_gsw_block_sweep's score_kind (3, the
-    logistic regression: the wide sweep only), or None (per-row path)."""
+    logistic regression: the wide sweep only), or None (per-row path).  The
+    walks refresh a score from all of the data, so a minibatch target (a
+    LogisticRegression with a batch, like BayesianNN) takes the per-row path,
+    its window scored through the one-particle call."""
     from .targets import Gaussian, GaussianMixture1D, LogisticRegression
     if target is None:
         return 0
@@ -1269,7 +1272,7 @@ def _gs_score_kind(target):
     if isinstance(target, GaussianMixture1D):
         return 2
     if isinstance(target, LogisticRegression):
-        return 3
+        return 3 if target.batch is None else None
     return None
 
 
@@ -1288,7 +1291,8 @@ def sequential_sweep(X, S, rows, h_state, step, target=None, score_scale=1.0, ph
     d <= 64 with an elementwise target on the VALU form, 64 < d <= 1024 (and
     the logistic regression at any d <= 1024, its score refreshed in the
     walk) on the wide one; otherwise one row kernel (+ one score refresh) per
-    row.
+    row -- which is also where every minibatch target goes (the walks score
+    on all of the data).
 
     hold: a dict the caller owns.  The wide sweep's workspace is stored in it,
     so it lives as long as the dict does: a caller that captures the sweep in

@@ -19,8 +19,9 @@ Extensions (keyword-only, defaults keep the reference behaviour):
                       timestep into `sampler.diagnostics` (default off);
   adagrad             None (fixed steps), True or a dsvgd.AdaGrad: Liu &
                       Wang's AdaGrad-conditioned steps (order="jacobi").
-A target with minibatches (targets.BayesianNN(batch=...)) is scored on window
-t of its data at iteration t, in both orders.
+A target with minibatches (targets.BayesianNN(batch=...) or
+targets.LogisticRegression(batch=...)) is scored on window t of its data at
+iteration t, in both orders.
 The kernel must be RBF- or IMQ-shaped (see dsvgd.kernels); RBF("median") /
 IMQ("median") select the median-heuristic bandwidth h = median(D)/log(n),
 recomputed every iteration.

@@ -49,6 +49,64 @@ class BuiltinTarget(Target):
     """Targets whose score is a libdsvgd_hip kernel sequence (graph-capturable)."""
 
 
+class _Windowed(object):
+    """The minibatch window of a data target (BayesianNN, LogisticRegression):
+    batch=B with 1 <= B < N scores the cyclic window of B rows that starts at a
+    cursor kept on the device, one per device.  The host keeps only where a
+    cursor made from now on starts."""
+
+    def _init_batch(self, batch):
+        if batch is not None:
+            if isinstance(batch, bool) or int(batch) != batch or batch < 1:
+                raise ValueError("batch must be a positive integer (or None), got %r" % (batch,))
+            batch = int(batch) if batch < self.N else None    # the whole data: no window
+        self.batch = batch
+        self._cursor = {}     # device -> int64[1], the window's first row
+        self._origin = 0      # where a cursor made from now on starts
+        self._last = None     # the device of the last score call
+        self._full = None
+
+    @property
+    def full(self):
+        """The full-data target over the same tensors (itself without a batch)."""
+        if self.batch is None:
+            return self
+        if self._full is None:
+            twin = type(self).__new__(type(self))
+            twin.__dict__.update(self.__dict__)
+            twin.batch, twin._cursor, twin._full = None, {}, None
+            self._full = twin
+        return self._full
+
+    def _window(self, dev):
+        """The cursor of `dev` (made on first use, outside any capture: the
+        samplers' first iteration runs eagerly)."""
+        cur = self._cursor.get(dev)
+        if cur is None:
+            cur = self._cursor[dev] = torch.full((1,), self._origin, dtype=torch.int64, device=dev)
+        self._last = dev
+        return cur
+
+    def next_batch(self):
+        """The window of the device in use (the last one scored on) moves by
+        `batch` rows, on that device's current stream."""
+        if self.batch is None:
+            return
+        if self._last is None:     # no device yet: the first cursor starts a window on
+            self._origin = (self._origin + self.batch) % self.N
+            return
+        N.call("dsvgd_window_advance", N.ptr(self._cursor[self._last]), self.batch, self.N,
+               N.stream(self._last))
+
+    def reset_batch(self, t=0):
+        """Every cursor (and any made later) to iteration t's window, (t batch) mod N."""
+        if self.batch is None:
+            return
+        self._origin = (int(t) * self.batch) % self.N
+        for cur in self._cursor.values():
+            cur.fill_(self._origin)
+
+
 class Gaussian(BuiltinTarget):
     """N(mu, diag(1/lam)): log p = -1/2 sum_c lam_c (x_c - mu_c)^2 (+ const)."""
 
@@ -96,23 +154,33 @@ class GaussianMixture1D(BuiltinTarget):
                N.ld(out), N.stream(X.device))
 
 
-class LogisticRegression(BuiltinTarget):
+class LogisticRegression(_Windowed, BuiltinTarget):
     """Bayesian logistic regression of experiments/logreg.py:45-58.
 
     x = [log alpha, w] (d = 1 + p); alpha ~ Gamma(1, 1) (no log-Jacobian, as in
     the reference), w ~ N(0, I/alpha), labels t in {-1, +1}.
+
+    batch=B with 1 <= B < N scores a minibatch, by BayesianNN's rules: the
+    likelihood over the cyclic window of B rows that starts at a cursor kept
+    on the device, weighted N / B, the prior once (dsvgd_score_logreg_window,
+    exact fp32 whatever `gemm` is, for every n).  next_batch() moves the window
+    by B rows, reset_batch(t) puts it at (t B) mod N; `logp` stays the
+    full-data density and `full` is the full-data twin (evaluation,
+    dsvgd.metrics.ksd; it shares this target's prepared workspaces).
+    batch=None or batch >= N is the full-data target.
     """
 
     ENGINES = {"h2": 0, "x3": 1, "f32": 2}   # dsvgd_score_logreg_engine
     SMALL_ROWS = 32      # one-block-per-particle path (no workspace), csrc/logreg.hip
 
-    def __init__(self, x_train, t_train, gemm="h2"):
+    def __init__(self, x_train, t_train, gemm="h2", batch=None):
         self.x = torch.as_tensor(x_train, dtype=torch.float32)
         self.t = torch.as_tensor(t_train, dtype=torch.float32).reshape(-1)
         assert self.x.shape[0] == self.t.shape[0]
         if gemm not in self.ENGINES:
             raise ValueError("gemm must be one of %s" % sorted(self.ENGINES))
         self.gemm = gemm
+        self._init_batch(batch)
         self._dev = {}
         self._ws = {}             # workspace key -> buffer, least recently used first
         self._prepared = {}       # workspace key -> engine whose data image it holds
@@ -155,10 +223,14 @@ class LogisticRegression(BuiltinTarget):
         return self._dev[key]
 
     def fingerprint(self):
-        """Digest of the data (DistSampler: ranks whose targets agree on it
-        hold the same data, so their scores of a particle are the same)."""
+        """Digest of the data, and of the batch of a minibatch target
+        (DistSampler: ranks whose targets agree on it hold the same data, so
+        their scores of a particle are the same)."""
         import hashlib
+        import struct
         h = hashlib.sha1(b"logreg")
+        if self.batch is not None:
+            h.update(struct.pack("<q", self.batch))
         h.update(_host_bytes(self.x))
         h.update(_host_bytes(self.t))
         return h.hexdigest()
@@ -182,10 +254,20 @@ class LogisticRegression(BuiltinTarget):
     def score(self, X, out, scale=1.0, prior_weight=1.0):
         """out = scale * grad log p(X); prior_weight != 1 weighs the prior
         terms (DistSampler's gathered-data all_scores: the prior of S ranks'
-        logp, distsampler.py:160-170), on the prepared path only."""
+        logp, distsampler.py:160-170), on the prepared path only.  A minibatch
+        target scores its window for every n (no workspace) and refuses a
+        prior_weight: the gathered-data mode has no windows."""
         n, d = X.shape
         assert d == self.x.shape[1] + 1, "logreg target has d = 1 + p = %d" % (self.x.shape[1] + 1)
         xd, t = self._params(X.device)
+        if self.batch is not None:
+            if prior_weight != 1.0:
+                raise ValueError("prior_weight needs the full-data target (batch=None)")
+            N.call("dsvgd_score_logreg_window", N.ptr(X), N.ld(X), n, d, N.ptr(xd), N.ld(xd),
+                   N.ptr(t), self.N, float(scale), N.ptr(out), N.ld(out), None,
+                   self.ENGINES[self.gemm], N.ptr(self._window(X.device)), self.batch,
+                   N.stream(X.device))
+            return
         # one workspace per (device, n): the ones a captured HIP graph
         # (engine.StepGraph) holds are pinned and never freed behind it
         # (release() frees them explicitly); of the others the
@@ -227,7 +309,7 @@ class LogisticRegression(BuiltinTarget):
         self._pinned.clear()
 
 
-class BayesianNN(BuiltinTarget):
+class BayesianNN(_Windowed, BuiltinTarget):
     """Bayesian neural-network regression (Liu & Wang 2016): one hidden ReLU
     layer of `hidden` units, Gamma(a0, b0) hyper-priors on the noise precision
     gamma and the weight precision lambda (carried as logs, with the
@@ -259,16 +341,8 @@ class BayesianNN(BuiltinTarget):
         if not 1 <= self.p <= self.MAX_WIDTH:
             raise ValueError("x_train must have 1 to %d columns, got %d" % (self.MAX_WIDTH, self.p))
         self.a0, self.b0 = float(a0), float(b0)
-        if batch is not None:
-            if isinstance(batch, bool) or int(batch) != batch or batch < 1:
-                raise ValueError("batch must be a positive integer (or None), got %r" % (batch,))
-            batch = int(batch) if batch < self.N else None    # the whole data: no window
-        self.batch = batch
+        self._init_batch(batch)
         self._dev = {}
-        self._cursor = {}     # device -> int64[1], the window's first row
-        self._origin = 0      # where a cursor made from now on starts
-        self._last = None     # the device of the last score call
-        self._full = None
 
     @property
     def N(self):
@@ -277,46 +351,6 @@ class BayesianNN(BuiltinTarget):
     @property
     def p(self):
         return self.x.shape[1]
-
-    @property
-    def full(self):
-        """The full-data target over the same tensors (itself without a batch)."""
-        if self.batch is None:
-            return self
-        if self._full is None:
-            twin = BayesianNN.__new__(BayesianNN)
-            twin.__dict__.update(self.__dict__)
-            twin.batch, twin._cursor, twin._full = None, {}, None
-            self._full = twin
-        return self._full
-
-    def _window(self, dev):
-        """The cursor of `dev` (made on first use, outside any capture: the
-        samplers' first iteration runs eagerly)."""
-        cur = self._cursor.get(dev)
-        if cur is None:
-            cur = self._cursor[dev] = torch.full((1,), self._origin, dtype=torch.int64, device=dev)
-        self._last = dev
-        return cur
-
-    def next_batch(self):
-        """The window of the device in use (the last one scored on) moves by
-        `batch` rows, on that device's current stream."""
-        if self.batch is None:
-            return
-        if self._last is None:     # no device yet: the first cursor starts a window on
-            self._origin = (self._origin + self.batch) % self.N
-            return
-        N.call("dsvgd_window_advance", N.ptr(self._cursor[self._last]), self.batch, self.N,
-               N.stream(self._last))
-
-    def reset_batch(self, t=0):
-        """Every cursor (and any made later) to iteration t's window, (t batch) mod N."""
-        if self.batch is None:
-            return
-        self._origin = (int(t) * self.batch) % self.N
-        for cur in self._cursor.values():
-            cur.fill_(self._origin)
 
     @property
     def d(self):

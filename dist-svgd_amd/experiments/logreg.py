@@ -24,7 +24,12 @@ same RBF kernel exp(-|x-y|^2) (h = 1, logreg.py:60-61) and JKO step h = 10
 * plots: visdom is not available; `make_plots` writes the test-accuracy
   curve (dsvgd ensemble vs an sklearn logistic regression, logreg_plots.py:25-67)
   to `test_acc.csv` in the results directory, computed on the GPU
-  (dsvgd.metrics, the posterior-predictive mean of logreg_plots.py:42-50).
+  (dsvgd.metrics, the posterior-predictive mean of logreg_plots.py:42-50);
+* --batch B scores every rank's shard on a cyclic window of B rows weighted
+  N / B (dsvgd.targets.LogisticRegression(batch=B)) and --adagrad takes Liu &
+  Wang's AdaGrad-conditioned steps (--order jacobi only, as the samplers
+  enforce) -- their published logistic-regression setting is batch 100 with
+  AdaGrad.  Both default to off: every existing result stands.
 """
 import os
 import shutil
@@ -87,8 +92,12 @@ def load_dataset(dataset_name, fold, data_dir=None):
 
 
 def run(rank, num_shards, dataset_name, fold, nparticles, niter, stepsize, exchange, wasserstein,
-        results_dir, data_dir=None, order="sequential", device=None, timings=None):
-    """One rank of the experiment (logreg.py:23-92)."""
+        results_dir, data_dir=None, order="sequential", device=None, timings=None, batch=None,
+        adagrad=False, curve=False):
+    """One rank of the experiment (logreg.py:23-92).  batch: rows per
+    minibatch window of this rank's shard (None: all of them); adagrad:
+    AdaGrad-conditioned steps (order="jacobi"); curve: return this rank's
+    test-accuracy curve (a list of {timestep, dsvgd})."""
     torch.manual_seed(rank)
     dev = torch.device(device) if device is not None else torch.device(
         "cuda", rank % max(1, torch.cuda.device_count()))
@@ -96,7 +105,8 @@ def run(rank, num_shards, dataset_name, fold, nparticles, niter, stepsize, excha
     x_train, t_train, _, _ = load_dataset(dataset_name, fold, data_dir)
     samples_per_shard = int(x_train.shape[0] / num_shards)
     s, e = samples_per_shard * rank, samples_per_shard * (rank + 1)
-    target = dsvgd.targets.LogisticRegression(x_train[s:e], np.asarray(t_train[s:e], np.float32))
+    target = dsvgd.targets.LogisticRegression(x_train[s:e], np.asarray(t_train[s:e], np.float32),
+                                              batch=batch)
     d = 1 + x_train.shape[1]
 
     q = Normal(0, 1)
@@ -109,7 +119,7 @@ def run(rank, num_shards, dataset_name, fold, nparticles, niter, stepsize, excha
                                 exchange_particles=exchange in ['all_particles', 'all_scores'],
                                 exchange_scores=exchange == 'all_scores',
                                 include_wasserstein=wasserstein, order=order,
-                                lagged=LAGGED.get(exchange))
+                                lagged=LAGGED.get(exchange), adagrad=adagrad or None)
     m = sampler.particles.shape[0]
     hist = torch.empty(niter + 1, m, d, dtype=torch.float32, device=dev)
     torch.cuda.synchronize(dev)
@@ -125,8 +135,20 @@ def run(rank, num_shards, dataset_name, fold, nparticles, niter, stepsize, excha
         timings["wall_s"] = time.perf_counter() - t0
     vals = hist.cpu().numpy().reshape(-1, d)
     steps = np.repeat(np.arange(niter + 1), m)
-    pd.DataFrame({'timestep': steps, 'value': list(vals)}).to_pickle(
-        os.path.join(results_dir, 'shard-{}.pkl'.format(rank)))
+    df = pd.DataFrame({'timestep': steps, 'value': list(vals)})
+    df.to_pickle(os.path.join(results_dir, 'shard-{}.pkl'.format(rank)))
+    if curve:
+        _, _, x_test, t_test = load_dataset(dataset_name, fold, data_dir)
+        return accuracy_curve(df, x_test, t_test, dev)
+
+
+def accuracy_curve(df, x_test, t_test, device="cuda"):
+    """Per timestep the dsvgd posterior-predictive test accuracy (on the GPU)."""
+    rows = []
+    for t, g in df.groupby('timestep'):
+        P = torch.as_tensor(np.stack(g['value'].values), dtype=torch.float32, device=device)
+        rows.append({'timestep': int(t), 'dsvgd': dsvgd.metrics.test_accuracy(P, x_test, t_test)})
+    return rows
 
 
 def load_results(results_dir):
@@ -144,12 +166,8 @@ def test_accuracy_curve(df, x_train, t_train, x_test, t_test, device="cuda"):
     from sklearn.linear_model import LogisticRegression
     baseline = (LogisticRegression().fit(x_train, np.asarray(t_train).reshape(-1))
                 .score(x_test, np.asarray(t_test).reshape(-1)))
-    rows = []
-    for t, g in df.groupby('timestep'):
-        P = torch.as_tensor(np.stack(g['value'].values), dtype=torch.float32, device=device)
-        rows.append({'timestep': int(t),
-                     'dsvgd': dsvgd.metrics.test_accuracy(P, x_test, t_test),
-                     'sklearn logreg': baseline})
+    rows = [dict(r, **{'sklearn logreg': baseline})
+            for r in accuracy_curve(df, x_test, t_test, device)]
     return pd.DataFrame(rows)
 
 
@@ -164,16 +182,17 @@ def make_plots(dataset, fold, nproc, nparticles, stepsize, exchange, wasserstein
     return acc
 
 
-def _init_distributed(rank, nproc, port, args):
+def _init_distributed(rank, nproc, port, args, run_kw=None):
+    """One spawned rank: args and run_kw are run()'s (batch, adagrad)."""
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
     os.environ['MASTER_PORT'] = str(port)
     backend = 'nccl' if torch.cuda.device_count() >= nproc else 'gloo'
-    kw = {}
+    pg_kw = {}
     if backend == 'nccl':
-        kw['device_id'] = torch.device('cuda', rank)
-    dist.init_process_group(backend, rank=rank, world_size=nproc, **kw)
+        pg_kw['device_id'] = torch.device('cuda', rank)
+    dist.init_process_group(backend, rank=rank, world_size=nproc, **pg_kw)
     try:
-        run(rank, nproc, *args)
+        run(rank, nproc, *args, **(run_kw or {}))
     finally:
         dist.destroy_process_group()
 
@@ -196,8 +215,12 @@ def _init_distributed(rank, nproc, port, args):
               help='sequential = the reference Gauss-Seidel sweep; jacobi = the MFMA fast path')
 @click.option('--results-dir', default=None, help='default: $DSVGD_RESULTS_DIR or ./results')
 @click.option('--data-dir', default=None, help='directory holding benchmarks.mat')
+@click.option('--batch', type=click.IntRange(min=1), default=None,
+              help="rows per minibatch window of each rank's shard (default: all of them)")
+@click.option('--adagrad/--no-adagrad', default=False,
+              help='AdaGrad-conditioned steps (--order jacobi only)')
 def cli(dataset, fold, nproc, nparticles, niter, stepsize, exchange, wasserstein, master_addr,
-        master_port, plots, order, results_dir, data_dir):
+        master_port, plots, order, results_dir, data_dir, batch, adagrad):
     """logreg.py:96-140: clean the results directory, run the ranks, plot."""
     world = int(os.environ.get('WORLD_SIZE', '0'))
     if world > 0:            # launched by torchrun: this process is one rank
@@ -211,22 +234,23 @@ def cli(dataset, fold, nproc, nparticles, niter, stepsize, exchange, wasserstein
         os.makedirs(rdir)
     args = (dataset, fold, nparticles, niter, stepsize, exchange, wasserstein, rdir, data_dir,
             order)
+    run_kw = dict(batch=batch, adagrad=adagrad)
     if world > 0:
         local = int(os.environ.get('LOCAL_RANK', rank))
         backend = 'nccl' if torch.cuda.device_count() >= world else 'gloo'
-        kw = {'device_id': torch.device('cuda', local)} if backend == 'nccl' else {}
-        dist.init_process_group(backend, **kw)
+        pg_kw = {'device_id': torch.device('cuda', local)} if backend == 'nccl' else {}
+        dist.init_process_group(backend, **pg_kw)
         dist.barrier()
-        run(rank, world, *args, device='cuda:%d' % (local % torch.cuda.device_count()))
+        run(rank, world, *args, device='cuda:%d' % (local % torch.cuda.device_count()), **run_kw)
         dist.barrier()
         dist.destroy_process_group()
         if rank != 0:
             return
     elif nproc == 1:
-        run(0, 1, *args)
+        run(0, 1, *args, **run_kw)
     else:
         os.environ['MASTER_ADDR'] = master_addr
-        torch.multiprocessing.spawn(_init_distributed, args=(nproc, master_port, args),
+        torch.multiprocessing.spawn(_init_distributed, args=(nproc, master_port, args, run_kw),
                                     nprocs=nproc, join=True)
     if plots:
         acc = make_plots(dataset, fold, nproc, nparticles, stepsize, exchange, wasserstein,

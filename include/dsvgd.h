@@ -862,6 +862,36 @@ int dsvgd_score_logreg_prior(const float* X, int64_t ldx, int64_t n, int64_t d, 
                              float scale, float prior_weight, float* S, int64_t lds,
                              void* workspace, int engine, void* stream);
 
+/* The minibatch estimate of the logistic-regression score: the likelihood
+ * over the cyclic window of B data rows that starts at row c = *cursor, rows
+ * (c + q) mod N for q < B, its terms weighted N / B, and the prior terms once;
+ * scale applies to the sum:
+ *   s_w = scale*((N/B) sum_q t_q sigma(-t_q xd_q.w) xd_q - a w),
+ *   s_0 = scale*(-a + p/2 - a/2 |w|^2)            (dsvgd_score_logreg's)
+ * cursor: one int64 in device memory, read by every workgroup (any value:
+ * taken mod N), so that a captured iteration replays with a moving window --
+ * the window rule of dsvgd_score_bnn_window; dsvgd_window_advance moves it.
+ * The arguments of dsvgd_score_logreg_engine, then the cursor and B.  The
+ * window's rows are read where they lie on every call (no prepared image):
+ * exact fp32 on v_mfma_f32_32x32x2_f32, a workgroup per 128 particles, the
+ * window through LDS in chunks of 32 rows, G in registers; p > 256 splits the
+ * columns over workgroups; n <= 16 (the sequential order's one-particle
+ * refresh) takes a workgroup per particle on the VALU.  Every sum in a fixed
+ * order, no atomics: the same bits on every call.  `engine` is checked (0-2)
+ * and otherwise unused -- every engine's window score is this fp32 kernel --
+ * and `workspace` is not read (may be NULL):
+ * dsvgd_logreg_window_workspace_bytes is 0 and exists for callers that size
+ * every score workspace through a query.  Only enqueues work.  Any n >= 1,
+ * 1 <= p = d - 1 <= 1023, 1 <= B <= N; ldx, lds >= d, ldxd >= p; S's pad
+ * columns are left alone.  Replaces: the reference has no minibatch logp;
+ * its users subsample inside a Python logp differentiated by autograd
+ * (dsvgd/sampler.py:28-33 _dlogp; notes.md:10-34). */
+size_t dsvgd_logreg_window_workspace_bytes(int64_t n, int64_t B, int64_t p);
+int dsvgd_score_logreg_window(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Xd,
+                              int64_t ldxd, const float* t, int64_t N, float scale, float* S,
+                              int64_t lds, void* workspace, int engine, const int64_t* cursor,
+                              int64_t B, void* stream);
+
 /* Posterior-predictive probability of the logistic-regression test set:
  * prob[q] = (1/n) sum_j sigma(xt_q . w_j), w_j = X[j][1:d] (no bias; alpha
  * unused) -- the ensemble mean of experiments/logreg_plots.py:42-50
