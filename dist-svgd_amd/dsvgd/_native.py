@@ -176,6 +176,10 @@ SIGNATURES = {
     "dsvgd_score_bnn_window": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _f, _f,
                                       _f, _p, _i64, _p, _i64, _p]),
     "dsvgd_window_advance": (_int, [_p, _i64, _i64, _p]),
+    # the Gaussian mixture with diagonal precisions (csrc/gmix.hip)
+    "dsvgd_score_gmix": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _f, _p, _i64,
+                                _p]),
+    "dsvgd_gmix_assign": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p]),
     # the AdaGrad-conditioned update (csrc/adagrad.hip)
     "dsvgd_adagrad_step": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _f, _f, _f, _p]),
     # the wide blocked Gauss-Seidel sweep (ABI 4)

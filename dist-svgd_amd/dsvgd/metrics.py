@@ -17,6 +17,11 @@ reference; csrc/ksd.hip).
 Bayesian neural-network regression target (dsvgd.targets.BayesianNN) on a
 test set: every particle's predictions in `dsvgd_bnn_predict` (csrc/bnn.hip),
 the two reductions over them in fp64 torch on the device.
+
+`gmix_logp` and `mode_shares` evaluate particles under a
+dsvgd.targets.GaussianMixture: every particle's log density and its most
+responsible component in `dsvgd_gmix_assign` (csrc/gmix.hip), the shares by a
+bincount on the device.
 """
 import math
 
@@ -123,6 +128,34 @@ def bnn_loglik(particles, target, x_test, y_test):
     lg = torch.as_tensor(particles)[:, -2].to(device=dev, dtype=torch.float64)
     comp = 0.5 * (lg[:, None] - math.log(2.0 * math.pi)) - 0.5 * torch.exp(lg)[:, None] * (y - F) ** 2
     return float((torch.logsumexp(comp, 0) - math.log(F.shape[0])).mean())
+
+
+def _gmix_assign(particles, target):
+    from .targets import GaussianMixture
+    if not isinstance(target, GaussianMixture):
+        raise ValueError("target must be a dsvgd.targets.GaussianMixture")
+    X = torch.as_tensor(particles)
+    if X.dim() != 2 or X.shape[1] != target.d:
+        raise ValueError("particles must be (n, d) with d = %d, got shape %s"
+                         % (target.d, tuple(X.shape)))
+    dev = N.require_gpu(X.device if X.is_cuda else "cuda")
+    return target.assign(_device_f32(X, dev))
+
+
+def gmix_logp(particles, target):
+    """(n,) device tensor: the normalised log density of every particle under
+    the dsvgd.targets.GaussianMixture `target` (dsvgd_gmix_assign)."""
+    return _gmix_assign(particles, target)[0]
+
+
+def mode_shares(particles, target):
+    """(K,) device tensor (fp64): the fraction of the particles whose most
+    responsible component is k -- the mode-coverage diagnostic, to compare
+    with `target.weights`.  The components come from dsvgd_gmix_assign (the
+    lowest index on a tie), the count is torch.bincount on the device."""
+    comp = _gmix_assign(particles, target)[1]
+    counts = torch.bincount(comp.long(), minlength=target.K)
+    return counts.double() / comp.numel()
 
 
 def predictive_prob(particles, x_test):

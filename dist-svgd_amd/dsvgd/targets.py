@@ -8,7 +8,9 @@ particles in one batched device call:
 * built-in targets run hand-written gfx950 kernels (libdsvgd_hip.so):
   :class:`Gaussian`, :class:`GaussianMixture1D` (experiments/gmm.py:16-21),
   :class:`LogisticRegression` (experiments/logreg.py:45-58, two MFMA GEMMs),
-  :class:`BayesianNN` (beyond the reference: one kernel, csrc/bnn.hip);
+  :class:`BayesianNN` (beyond the reference: one kernel, csrc/bnn.hip),
+  :class:`GaussianMixture` (K components with diagonal precisions in d
+  dimensions: one kernel, csrc/gmix.hip);
 * any other `logp` callable is wrapped by :class:`CallableTarget`, which runs
   the user's own torch code under ``torch.func.vmap(torch.func.grad(logp))``
   on the particles' device (user code, not a dsvgd compute path).
@@ -18,6 +20,7 @@ so it can be handed to the reference implementation unchanged.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -404,6 +407,113 @@ class BayesianNN(_Windowed, BuiltinTarget):
         N.call("dsvgd_score_bnn", N.ptr(X), N.ld(X), n, d, N.ptr(z), N.ld(z), N.ptr(y), self.N,
                self.p, self.hidden, self.a0, self.b0, float(scale), N.ptr(out), N.ld(out),
                N.stream(X.device))
+
+
+class GaussianMixture(BuiltinTarget):
+    """sum_k w~_k N(x; mu_k, diag(1 / lam_k)) in d dimensions, w~ = w / sum(w).
+
+    means: (K, d); precisions: anything that broadcasts to (K, d), finite and
+    > 0 (default 1); weights: (K,), finite and > 0 (default equal), normalised
+    here: `weights` holds w~ in fp64.  d <= 1024.
+
+    The score is one kernel (csrc/gmix.hip): one pass over the components with
+    a running maximum, so any K, and finite scores however far a particle is
+    from every mode.  `assign` gives every particle's log density and its most
+    responsible component (dsvgd.metrics.gmix_logp / mode_shares)."""
+
+    MAX_D = 1024    # dsvgd_score_gmix
+
+    def __init__(self, means, precisions=1.0, weights=None):
+        self.means = torch.as_tensor(means).detach().to(torch.float32)
+        if self.means.dim() != 2 or self.means.shape[0] < 1 or self.means.shape[1] < 1:
+            raise ValueError("means must be (K, d) with K, d >= 1, got shape %s"
+                             % (tuple(self.means.shape),))
+        if not bool(torch.isfinite(self.means).all()):
+            raise ValueError("means must be finite")
+        K, d = self.means.shape
+        if d > self.MAX_D:
+            raise ValueError("GaussianMixture supports d <= %d, got %d" % (self.MAX_D, d))
+        lam = torch.as_tensor(precisions).detach().to(torch.float32)
+        try:
+            lam = torch.broadcast_to(lam, (K, d))
+        except RuntimeError:
+            raise ValueError("precisions must broadcast to (K, d) = %s, got shape %s"
+                             % ((K, d), tuple(lam.shape))) from None
+        if not bool((torch.isfinite(lam) & (lam > 0)).all()):
+            raise ValueError("precisions must be finite and > 0")
+        self.precisions = lam.contiguous()
+        if weights is not None and not isinstance(weights, torch.Tensor):
+            try:
+                weights = np.asarray(weights, dtype=np.float64)   # Python floats keep their fp64
+            except (TypeError, ValueError):
+                raise ValueError("weights must be (K,) numbers") from None
+        w = torch.ones(K, dtype=torch.float64) if weights is None else \
+            torch.as_tensor(weights).detach().to(device="cpu", dtype=torch.float64)
+        if tuple(w.shape) != (K,):
+            raise ValueError("weights must be (K,) = (%d,), got shape %s" % (K, tuple(w.shape)))
+        if not bool((torch.isfinite(w) & (w > 0)).all()):
+            raise ValueError("weights must be finite and > 0")
+        self.weights = w / w.sum()
+        # c_k = log w~_k + 1/2 sum_c log lam_kc, in fp64 on the host
+        self._c = torch.log(self.weights) + 0.5 * torch.log(self.precisions.double().cpu()).sum(1)
+        self._dev = {}
+
+    @property
+    def K(self):
+        return self.means.shape[0]
+
+    @property
+    def d(self):
+        return self.means.shape[1]
+
+    def logp(self, x):
+        """The normalised log density of one particle x (d,), in x's dtype."""
+        if x.shape[-1] != self.d:
+            raise ValueError("GaussianMixture target has d = %d" % self.d)
+        mu = self.means.to(device=x.device, dtype=x.dtype)
+        lam = self.precisions.to(device=x.device, dtype=x.dtype)
+        c = self._c.to(device=x.device, dtype=x.dtype)
+        q = 0.5 * (lam * (x - mu) ** 2).sum(-1)
+        return torch.logsumexp(c - q, -1) - 0.5 * self.d * math.log(2.0 * math.pi)
+
+    def _params(self, dev):
+        """(means, precisions, c) on dev, made on first use (outside any
+        capture: the samplers' first iteration runs eagerly)."""
+        if dev not in self._dev:
+            self._dev[dev] = (self.means.to(dev).contiguous(), self.precisions.to(dev).contiguous(),
+                              self._c.to(device=dev, dtype=torch.float32).contiguous())
+        return self._dev[dev]
+
+    def fingerprint(self):
+        """Digest of K, d, the means, the precisions and the normalised weights."""
+        import hashlib
+        import struct
+        h = hashlib.sha1(b"gmix")
+        h.update(struct.pack("<qq", self.K, self.d))
+        for t in (self.means, self.precisions, self.weights):
+            h.update(_host_bytes(t))
+        return h.hexdigest()
+
+    def score(self, X, out, scale=1.0):
+        n, d = X.shape
+        assert d == self.d, "GaussianMixture target has d = %d" % self.d
+        mu, lam, c = self._params(X.device)
+        N.call("dsvgd_score_gmix", N.ptr(X), N.ld(X), n, d, N.ptr(mu), N.ld(mu), N.ptr(lam),
+               N.ld(lam), N.ptr(c), self.K, float(scale), N.ptr(out), N.ld(out),
+               N.stream(X.device))
+
+    def assign(self, X):
+        """(logp (n,) float32, comp (n,) int32) on X's device: every particle's
+        normalised log density and its most responsible component, the lowest
+        index on a tie (dsvgd_gmix_assign)."""
+        n, d = X.shape
+        assert d == self.d, "GaussianMixture target has d = %d" % self.d
+        mu, lam, c = self._params(X.device)
+        logp = torch.empty(n, dtype=torch.float32, device=X.device)
+        comp = torch.empty(n, dtype=torch.int32, device=X.device)
+        N.call("dsvgd_gmix_assign", N.ptr(X), N.ld(X), n, d, N.ptr(mu), N.ld(mu), N.ptr(lam),
+               N.ld(lam), N.ptr(c), self.K, N.ptr(logp), N.ptr(comp), N.stream(X.device))
+        return logp, comp
 
 
 class CallableTarget(Target):

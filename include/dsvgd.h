@@ -943,6 +943,30 @@ int dsvgd_bnn_predict(const float* X, int64_t ldx, int64_t n, int64_t d, const f
                       int64_t ldz, int64_t Nt, int64_t p, int64_t H, float* F, int64_t ldf,
                       void* stream);
 
+/* ---- Gaussian mixture with diagonal precisions (csrc/gmix.hip) ------------
+ *   p(x) = sum_k w~_k N(x; mu_k, diag(1/lam_k)),  w~ = w / sum(w)
+ *   c_k  = log w~_k + 1/2 sum_c log lam_kc         (the caller's, from fp64)
+ *   q_ik = 1/2 sum_c lam_kc (x_ic - mu_kc)^2,  l_ik = c_k - q_ik,
+ *   r_ik = softmax_k(l_ik),  S_ic = sum_k r_ik lam_kc (mu_kc - x_ic),
+ *   log p(x_i) = logsumexp_k l_ik - (d/2) log(2 pi).
+ * mu, lam: K x d row-major (ldm, ldl >= d), c: K floats.  Exact fp32 in the
+ * difference form lam (x - mu)^2; one pass over the components in ascending
+ * order with a running maximum (no exponent is taken without it: a particle
+ * far from every mode keeps a finite score), so K needs no workspace.  No
+ * atomics: the same bits on every call, and a particle's result depends
+ * neither on n nor on its row.  Any n >= 1, 1 <= K <= 2^30, 1 <= d <= 1024.
+ * Replaces a user logp of this model under autograd (the reference's
+ * experiments/gmm.py is the case K = 2, d = 1). */
+int dsvgd_score_gmix(const float* X, int64_t ldx, int64_t n, int64_t d, const float* mu,
+                     int64_t ldm, const float* lam, int64_t ldl, const float* c, int64_t K,
+                     float scale, float* S, int64_t lds, void* stream);
+/* The same pass without the score: logp_out[i] = log p(x_i) (normalised) and
+ * comp_out[i] = argmax_k l_ik, the most responsible component, the lowest
+ * index on a tie (n floats, n int32). */
+int dsvgd_gmix_assign(const float* X, int64_t ldx, int64_t n, int64_t d, const float* mu,
+                      int64_t ldm, const float* lam, int64_t ldl, const float* c, int64_t K,
+                      float* logp_out, int32_t* comp_out, void* stream);
+
 /* ---- AdaGrad-conditioned update of the Jacobi order (csrc/adagrad.hip) ----
  * Liu & Wang's rule, per entry of the m moved rows; p = phi (m x d, ldphi) is
  * the whole direction, the h * W2 rows included:
