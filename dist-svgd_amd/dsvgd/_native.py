@@ -242,6 +242,11 @@ SIGNATURES = {
                                     _i64, _p, _k, _int, _i64, _p, _p, _p, _p, _p]),
     "dsvgd_ksd_direct_kern": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _k,
                                      _p]),
+    # the maximum mean discrepancy between two particle sets (csrc/mmd.hip)
+    "dsvgd_mmd_parts": (_i64, [_i64, _int, _i64]),
+    "dsvgd_mmd_workspace_doubles": (_c.c_size_t, [_i64]),
+    "dsvgd_mmd_rows": (_int, [_p, _i64, _i64, _i64, _p, _k, _int, _i64, _i64, _p, _p]),
+    "dsvgd_mmd_finish": (_int, [_p, _i64, _i64, _int, _i64, _i64, _p, _p, _p, _p, _p, _p]),
 }
 
 

@@ -350,6 +350,7 @@ class PhiEngine(object):
         self.plan = None
         self.score_scale = None   # of the scores in Y (the last pack / pack_scores)
         self._ksd = None          # ksd()'s workspaces, allocated on first use
+        self._mmd = None          # mmd()'s, likewise
         if pair_split is not None:
             self._init_pair_split(*pair_split)
         self.k_rank = (m * n - 1) // 2 if (local_median and m < n) else -1
@@ -1162,6 +1163,64 @@ class PhiEngine(object):
             assert out.shape == (4,) and out.dtype == torch.float64
             out.copy_(W["out"])
         return (out, W["rows"].clone()) if rows else out
+
+    # --------------------------------------------------------------- MMD --
+    def mmd(self, n_first, rows=False, out=None, *, parts=None):
+        """Maximum mean discrepancy between the first n_first packed particles
+        (P) and the remaining n - n_first (Q), from the D and the bandwidth of
+        this engine (include/dsvgd.h; DESIGN.md 3, "The MMD two-sample
+        diagnostic"): after pack(Z) of the pooled set, distances() and a
+        bandwidth -- no direction() and no scores are needed.  One sweep over
+        D and an n-row finish.
+
+        Returns a 5-element float64 device tensor [PP, PQ, QQ, V, U] (the
+        class sums of the off-diagonal kernel values, MMD^2 as a V-statistic
+        and as the unbiased U-statistic; U is NaN if either set has one
+        point), written into `out` if given, without a host sync; with
+        rows=True also the (n,) fp32 rows rP, rQ and the witness.  The
+        workspaces are allocated on the first call and kept: later calls only
+        launch.  parts: force the sweep's slice count (dsvgd_mmd_parts; tests).
+
+        Needs the whole matrix (m == n, row0 == 0) in the row-block layout (no
+        pair split)."""
+        if self.plan is not None:
+            raise ValueError("mmd() does not support the pair-split layout")
+        if self.m != self.n or self.row0 != 0:
+            raise ValueError("mmd() needs the whole matrix (m == n, row0 == 0), got a row block "
+                             "m = %d, row0 = %d of n = %d" % (self.m, self.row0, self.n))
+        n_first = int(n_first)
+        if not 1 <= n_first < self.n:
+            raise ValueError("n_first must be in [1, n) = [1, %d), got %d" % (self.n, n_first))
+        lib = N.load()
+        s = N.stream(self.device)
+        sym = int(self.sym)
+        force = 0 if parts is None else int(parts)
+        key = (sym, force)
+        if self._mmd is None or self._mmd["key"] != key:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            np_ = int(lib.dsvgd_mmd_parts(self.n, sym, force))
+            self._mmd = dict(key=key, parts=np_, out=torch.empty(5, **f64),
+                             P=torch.empty(np_ * 2 * self.n_pad, **f32),
+                             rp=torch.empty(self.n, **f32), rq=torch.empty(self.n, **f32),
+                             witness=torch.empty(self.n, **f32),
+                             ws=torch.empty(int(lib.dsvgd_mmd_workspace_doubles(self.n)), **f64))
+        W = self._mmd
+        with span(self.timer, "mmd_rows"):
+            N.call("dsvgd_mmd_rows", N.ptr(self.D), self.n_pad, self.n, n_first, self.state.ptr,
+                   self._kern, sym, W["parts"], force, N.ptr(W["P"]), s)
+        with span(self.timer, "mmd_finish"):
+            N.call("dsvgd_mmd_finish", N.ptr(W["P"]), self.n, n_first, sym, W["parts"], force,
+                   N.ptr(W["rp"]), N.ptr(W["rq"]), N.ptr(W["witness"]), N.ptr(W["ws"]),
+                   N.ptr(W["out"]), s)
+        if out is None:
+            out = W["out"].clone()
+        else:
+            assert out.shape == (5,) and out.dtype == torch.float64
+            out.copy_(W["out"])
+        if rows:
+            return out, W["rp"].clone(), W["rq"].clone(), W["witness"].clone()
+        return out
 
     # ------------------------------------------------------------ helpers --
     def step(self, X, S, X_own=None, step=0.0, h=None, score_scale=1.0, allreduce=None,

@@ -476,6 +476,25 @@ class GaussianMixture(BuiltinTarget):
         q = 0.5 * (lam * (x - mu) ** 2).sum(-1)
         return torch.logsumexp(c - q, -1) - 0.5 * self.d * math.log(2.0 * math.pi)
 
+    def sample(self, m, seed=None, device=None):
+        """m exact draws as an (m, d) fp32 tensor (on `device` if given, else
+        on the host): a component k from the normalised weights, then mu_k +
+        eps / sqrt(lam_k), eps ~ N(0, I).  Drawn with a torch.Generator on the
+        CPU, so a seed gives the same draws on every machine and device
+        (seed=None: a fresh random seed).  The reference set of
+        dsvgd.metrics.mmd."""
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1:
+            raise ValueError("m must be an integer >= 1, got %r" % (m,))
+        g = torch.Generator(device="cpu")
+        if seed is None:
+            g.seed()
+        else:
+            g.manual_seed(int(seed))
+        comp = torch.multinomial(self.weights, int(m), replacement=True, generator=g)
+        eps = torch.randn(int(m), self.d, generator=g, dtype=torch.float32)
+        x = self.means.cpu()[comp] + eps / torch.sqrt(self.precisions.cpu()[comp])
+        return x if device is None else x.to(device)
+
     def _params(self, dev):
         """(means, precisions, c) on dev, made on first use (outside any
         capture: the samplers' first iteration runs eagerly)."""

@@ -16,7 +16,12 @@ Every `--every` iterations the mode shares of the particles (the fraction
 whose most responsible component is k, dsvgd.metrics.mode_shares) are printed
 beside the weights, with the mean log density (dsvgd.metrics.gmix_logp); at
 the end the kernelized Stein discrepancy of the final particles
-(dsvgd.metrics.ksd).  No plots.
+(dsvgd.metrics.ksd).  With `--mmd M` the particles are also compared with M
+exact draws of the mixture (drawn once, GaussianMixture.sample): every printed
+iteration gains the maximum mean discrepancy to them (dsvgd.metrics.mmd, the
+unbiased statistic at the pooled-median bandwidth), which -- unlike the
+score-based KSD -- sees wrong mode shares; the final one is printed before the
+final KSD.  No plots.
 """
 import os
 import sys
@@ -57,9 +62,12 @@ def _shares(v):
 
 
 def run(nparticles=50, niter=500, stepsize=1.0, every=100, d=1, modes=2, spread=2.0,
-        order="sequential", kernel="rbf", seed=42, device="cuda:0", out=print):
+        order="sequential", kernel="rbf", seed=42, device="cuda:0", out=print, mmd=0):
     """Runs the experiment; returns the recorded curve as a list of dicts
-    (iteration, shares, logp) and the final KSD."""
+    (iteration, shares, logp -- and mmd, against `mmd` exact draws, if mmd >
+    0) and the final KSD."""
+    if mmd < 0:
+        raise ValueError("mmd must be >= 0 (the number of exact draws; 0: off)")
     means, precisions, weights = mixture(d, modes, spread, seed)
     target = dsvgd.targets.GaussianMixture(means, precisions, weights)
     kern = make_kernel(kernel)
@@ -68,6 +76,7 @@ def run(nparticles=50, niter=500, stepsize=1.0, every=100, d=1, modes=2, spread=
     df = sampler.sample(nparticles, niter, stepsize, order=order, device=device, verbose=False)
     hist = np.stack(df["value"].to_list()).reshape(niter + 1, nparticles, d)
     out("weights %s" % _shares(target.weights.tolist()))
+    exact = target.sample(mmd, seed=seed, device=device) if mmd > 0 else None
     curve = []
     for it in sorted(set(range(0, niter + 1, every)) | {niter}):
         P = torch.as_tensor(hist[it], dtype=torch.float32, device=device)
@@ -75,7 +84,13 @@ def run(nparticles=50, niter=500, stepsize=1.0, every=100, d=1, modes=2, spread=
                "shares": dsvgd.metrics.mode_shares(P, target).cpu().tolist(),
                "logp": float(dsvgd.metrics.gmix_logp(P, target).double().mean())}
         curve.append(row)
-        out("iteration %5d  shares %s  mean logp %.4f" % (it, _shares(row["shares"]), row["logp"]))
+        line = "iteration %5d  shares %s  mean logp %.4f" % (it, _shares(row["shares"]), row["logp"])
+        if exact is not None:
+            row["mmd"] = dsvgd.metrics.mmd(P, exact, device=device)
+            line += "  mmd %.6g" % row["mmd"]
+        out(line)
+    if exact is not None:
+        out("final mmd %.6g" % curve[-1]["mmd"])
     ksd = dsvgd.metrics.ksd(hist[niter], target, kern, device=device)
     out("final ksd %.6g" % ksd)
     return curve, ksd
@@ -92,8 +107,10 @@ def run(nparticles=50, niter=500, stepsize=1.0, every=100, d=1, modes=2, spread=
 @click.option('--kernel', type=click.Choice(['rbf', 'imq']), default='rbf')
 @click.option('--every', type=int, default=100, help='print the diagnostics every k iterations')
 @click.option('--seed', type=int, default=42)
-def cli(d, modes, spread, nparticles, niter, stepsize, order, kernel, every, seed):
-    run(nparticles, niter, stepsize, every, d, modes, spread, order, kernel, seed)
+@click.option('--mmd', type=int, default=0,
+              help='compare with this many exact draws of the mixture (0: off)')
+def cli(d, modes, spread, nparticles, niter, stepsize, order, kernel, every, seed, mmd):
+    run(nparticles, niter, stepsize, every, d, modes, spread, order, kernel, seed, mmd=mmd)
 
 
 if __name__ == "__main__":

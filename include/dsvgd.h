@@ -1149,6 +1149,46 @@ int dsvgd_ksd_direct_kern(const float* Y, int64_t ldy, int64_t dp, int64_t d, in
                           int64_t m, int64_t n, const dsvgd_select_state* st, float* rows,
                           double* ws, double* out, dsvgd_kernel kern, void* stream);
 
+/* ---- maximum mean discrepancy between two particle sets (csrc/mmd.hip) ---
+ * (absent in the reference.)  The pooled set Z = [P; Q] of N = n_first + m
+ * particles is packed as one interacting set; D is its N x N distance matrix
+ * (the whole matrix: full panel layout, or the symmetric layout of
+ * dsvgd_sqdist_{h2,x3} layout 1), k the RBF or IMQ kernel at the bandwidth in
+ * st.  With
+ *   rP_i = sum_{j < n_first, j != i} k_ij,   rQ_i = sum_{j >= n_first, j != i} k_ij,
+ *   PP = sum_{i < n_first} rP_i,  PQ = sum_{i < n_first} rQ_i,  QQ = sum_{i >= n_first} rQ_i,
+ * and n = n_first, m = N - n_first:
+ *   V = (PP + n)/n^2 + (QQ + m)/m^2 - 2 PQ/(n m)         (k_ii = 1 exactly)
+ *   U = PP/(n (n-1)) + QQ/(m (m-1)) - 2 PQ/(n m)         (NaN if n = 1 or m = 1)
+ *   witness_i = (rP_i + [i < n])/n - (rQ_i + [i >= n])/m.
+ * The diagonal of D is never read.  No float atomics: every partial has a slot
+ * of its own and every sum a fixed order, so two calls give the same bits.
+ *
+ * dsvgd_mmd_rows: the one sweep over D.  P: `parts` slots of [rP | rQ], 2
+ * roundup(N,128) floats each, parts = dsvgd_mmd_parts(N, sym, force).  Full
+ * layout: slot z holds column slice z's sums.  Symmetric layout, T =
+ * roundup(N,128)/128, rparts = parts - T: slot z < rparts holds the row sums
+ * of slice z of each tile row's stored tiles (I, J >= I); slot rparts + I the
+ * column sums of the stored off-diagonal tiles of tile row I at the rows of J
+ * (the terms of the unwritten tile (J, I), each sent to rP or rQ by the class
+ * of its row i in I); entries of slot rparts + I at rows of tiles J <= I are
+ * never written nor read.  Pads (+inf) and the diagonal contribute exactly 0.
+ * dsvgd_mmd_parts: force <= 0: the slice count that fills the CUs (the rule
+ * of dsvgd_ksd_parts); force > 0: min(force, roundup(N,128)/128) row / column
+ * slices (tests: more than one slice on a small matrix, or one on a large).
+ * dsvgd_mmd_finish: the slots summed in slot order (fp64); rp, rq, witness
+ * (N floats each, nullable); ws: dsvgd_mmd_workspace_doubles(N) doubles (three
+ * per 64 rows); out[0..4] = PP, PQ, QQ, V, U (fp64 sums in a fixed two-level
+ * order). */
+int64_t dsvgd_mmd_parts(int64_t n_total, int sym, int64_t force);
+size_t dsvgd_mmd_workspace_doubles(int64_t n_total);
+int dsvgd_mmd_rows(const float* D, int64_t ldd, int64_t n_total, int64_t n_first,
+                   const dsvgd_select_state* st, dsvgd_kernel kern, int sym, int64_t parts,
+                   int64_t force, float* P, void* stream);
+int dsvgd_mmd_finish(const float* P, int64_t n_total, int64_t n_first, int sym, int64_t parts,
+                     int64_t force, float* rp, float* rq, float* witness, double* ws,
+                     double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
