@@ -66,6 +66,12 @@ __device__ __forceinline__ float pow2_inv(float s) {
 //   u^e 2^off = exp2(e log2(fma(D, 1/h, 1)) + off),   e < 0:
 // the +inf pads of D give log2 = +inf and exp2(-inf) = 0, as exp(-inf) does.
 constexpr int kFamRBF = DSVGD_KERNEL_RBF, kFamIMQ = DSVGD_KERNEL_IMQ;
+// a valid kernel description, and the one the plain (RBF) entry points pass on
+inline bool kern_ok(dsvgd_kernel k) {
+  return k.family == DSVGD_KERNEL_RBF ||
+         (k.family == DSVGD_KERNEL_IMQ && k.beta >= -1.f && k.beta < 0.f);
+}
+constexpr dsvgd_kernel kRbfKern = {DSVGD_KERNEL_RBF, 0.f};
 __device__ __forceinline__ float imq_pow(float v, float inv_h, float e, float off) {
   return __builtin_amdgcn_exp2f(fmaf(e, __builtin_amdgcn_logf(fmaf(v, inv_h, 1.f)), off));
 }

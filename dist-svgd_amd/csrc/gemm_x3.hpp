@@ -852,4 +852,22 @@ struct NTX3Tile {
   }
 };
 
+// ---- the NN engines' host entry points (phi.hip; logreg.hip's G . Xd) ----
+// C[splits x m x ldc] = f(A) B: A in panel layout (m_pad x K); B row-major
+// fp32 (nn_gemm), the FmtX3 image or the FmtH2 image with its column scales.
+// exp_: f is the kernel `fam` of A (IMQ: u^pw) with the diagonal (column
+// row0 + i) skipped and the row sums written; else f(a) = a.
+int nn_gemm(bool exp_, const float* A, int64_t K, const float* B, int64_t ldb, int64_t cols,
+            int splits, const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum,
+            int64_t m, int64_t row0, hipStream_t s, const float* gate, int fam = kFamRBF,
+            float pw = 0.f);
+int nn_x3_gemm(bool exp_, const float* A, int64_t K, const __bf16* Yx, int64_t ldy, int splits,
+               const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
+               int64_t row0, hipStream_t s, int sym, int m16, const float* gate,
+               int fam = kFamRBF, float pw = 0.f);
+int nn_h2_gemm(bool exp_, const float* A, int64_t K, const _Float16* Yh, int64_t ldy, int splits,
+               const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
+               int64_t row0, hipStream_t s, int sym, const float* colinv, const float* gate,
+               int fam = kFamRBF, float pw = 0.f);
+
 }  // namespace dsvgd

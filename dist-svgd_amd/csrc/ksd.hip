@@ -504,12 +504,6 @@ static int64_t ksd_row_parts(int64_t tiles, int64_t cap) {
 
 static bool a16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
-static bool kern_ok(dsvgd_kernel k) {
-  return k.family == DSVGD_KERNEL_RBF ||
-         (k.family == DSVGD_KERNEL_IMQ && k.beta >= -1.f && k.beta < 0.f);
-}
-static const dsvgd_kernel kRbfKern = {DSVGD_KERNEL_RBF, 0.f};
-
 }  // namespace dsvgd
 
 using namespace dsvgd;

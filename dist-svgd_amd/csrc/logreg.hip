@@ -18,15 +18,6 @@
 
 namespace dsvgd {
 
-int nn_gemm(bool exp_, const float* A, int64_t K, const float* B, int64_t ldb, int64_t cols,
-            int splits, const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum,
-            int64_t m, int64_t row0, hipStream_t s, const float* gate);
-int nn_x3_gemm(bool exp_, const float* A, int64_t K, const __bf16* Yx, int64_t ldy, int splits,
-               const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
-               int64_t row0, hipStream_t s, int sym, int m16, const float* gate);
-int nn_h2_gemm(bool exp_, const float* A, int64_t K, const _Float16* Yh, int64_t ldy, int splits,
-               const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
-               int64_t row0, hipStream_t s, int sym, const float* colinv, const float* gate);
 int h2_colscale(const float* A, int64_t lda, int64_t rows, int64_t cols, int64_t dp, float* ws, float* out,
                 hipStream_t s);
 int h2_ysplit(const float* Y, int64_t ldy, int64_t rows, const float* colscale, void* Yh,

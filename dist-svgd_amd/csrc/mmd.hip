@@ -322,11 +322,6 @@ __global__ __launch_bounds__(256) void mmd_reduce_kernel(const double* __restric
   }
 }
 
-static bool mmd_kern_ok(dsvgd_kernel k) {
-  return k.family == DSVGD_KERNEL_RBF ||
-         (k.family == DSVGD_KERNEL_IMQ && k.beta >= -1.f && k.beta < 0.f);
-}
-
 // the largest pooled set whose indices and panel offsets the kernels hold in
 // 32-bit ints (its D alone would be 4 TiB)
 constexpr int64_t kMmdMaxN = 1 << 20;
@@ -354,7 +349,7 @@ size_t dsvgd_mmd_workspace_doubles(int64_t n_total) {
 int dsvgd_mmd_rows(const float* D, int64_t ldd, int64_t n_total, int64_t n_first,
                    const dsvgd_select_state* st, dsvgd_kernel kern, int sym, int64_t parts,
                    int64_t force, float* P, void* stream) {
-  DSVGD_REQUIRE(mmd_kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
   DSVGD_REQUIRE(D && st && P, "null pointer");
   DSVGD_REQUIRE(n_total >= 2 && n_total <= kMmdMaxN, "sizes: 2 <= n_total <= 2^20");
   DSVGD_REQUIRE(n_first >= 1 && n_first < n_total, "sizes: 1 <= n_first < n_total");

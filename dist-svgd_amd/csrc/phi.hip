@@ -438,36 +438,28 @@ int nn_h2w_gemm(const float* D, int64_t K, const _Float16* Wh, int64_t dp, int s
 #endif
 }
 
+// The two split engines (declared in gemm_x3.hpp).  fam = IMQ (exp_ only):
+// the staging is K = u^pw, u = 1 + D/h (pw = beta: F, pw = beta - 1: G').
 int nn_x3_gemm(bool exp_, const float* A, int64_t K, const __bf16* Yx, int64_t ldy, int splits,
                const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
-               int64_t row0, hipStream_t s, int sym, int m16, const float* gate) {
+               int64_t row0, hipStream_t s, int sym, int m16, const float* gate, int fam,
+               float pw) {
+  if (fam == kFamIMQ)
+    return nn_split_gemm<FmtX3, kFamIMQ>(exp_, A, K, Yx, ldy, splits, st, C, ldc, rowsum, m, row0,
+                                         s, sym, m16, nullptr, gate, 1, pw);
   return nn_split_gemm<FmtX3>(exp_, A, K, Yx, ldy, splits, st, C, ldc, rowsum, m, row0, s, sym,
                               m16, nullptr, gate, 1);
 }
 
 int nn_h2_gemm(bool exp_, const float* A, int64_t K, const _Float16* Yh, int64_t ldy, int splits,
                const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum, int64_t m,
-               int64_t row0, hipStream_t s, int sym, const float* colinv, const float* gate) {
+               int64_t row0, hipStream_t s, int sym, const float* colinv, const float* gate,
+               int fam, float pw) {
+  if (fam == kFamIMQ)
+    return nn_split_gemm<FmtH2, kFamIMQ>(exp_, A, K, Yh, ldy, splits, st, C, ldc, rowsum, m, row0,
+                                         s, sym, 0, colinv, gate, 0, pw);
   return nn_split_gemm<FmtH2>(exp_, A, K, Yh, ldy, splits, st, C, ldc, rowsum, m, row0, s, sym, 0,
                               colinv, gate, 0);
-}
-
-// phi_mm's two split engines with the IMQ staging K = u^pw, u = 1 + D/h (pw =
-// beta: F, pw = beta - 1: G'); everything else as the two above with exp_.
-static int nn_x3_gemm_imq(const float* A, int64_t K, const __bf16* Yx, int64_t ldy, int splits,
-                          const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum,
-                          int64_t m, int64_t row0, hipStream_t s, int sym, int m16,
-                          const float* gate, float pw) {
-  return nn_split_gemm<FmtX3, kFamIMQ>(true, A, K, Yx, ldy, splits, st, C, ldc, rowsum, m, row0, s,
-                                       sym, m16, nullptr, gate, 1, pw);
-}
-
-static int nn_h2_gemm_imq(const float* A, int64_t K, const _Float16* Yh, int64_t ldy, int splits,
-                          const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum,
-                          int64_t m, int64_t row0, hipStream_t s, int sym, const float* colinv,
-                          const float* gate, float pw) {
-  return nn_split_gemm<FmtH2, kFamIMQ>(true, A, K, Yh, ldy, splits, st, C, ldc, rowsum, m, row0, s,
-                                       sym, 0, colinv, gate, 0, pw);
 }
 
 
@@ -1196,38 +1188,26 @@ int launch_nn(bool exp_, const float* A, const float* B, int64_t ldb, int64_t K,
 }
 
 // C[splits x m x cols] = f(A) B with A in panel layout (m_pad x K), B row-major K x cols.
-// exp_: f = exp2(-inv_h log2e a) with the diagonal (column row0 + i) skipped.
+// exp_: f = exp2(-inv_h log2e a) with the diagonal (column row0 + i) skipped;
+// fam = IMQ (exp_ only): f = u^pw, the exact f32 engine's IMQ staging.
 int nn_gemm(bool exp_, const float* A, int64_t K, const float* B, int64_t ldb, int64_t cols,
             int splits, const dsvgd_select_state* st, float* C, int64_t ldc, float* rowsum,
-            int64_t m, int64_t row0, hipStream_t s, const float* gate) {
+            int64_t m, int64_t row0, hipStream_t s, const float* gate, int fam, float pw) {
   // buffer-resource loads: 32-bit byte offsets from a block's A row panel
   // (K columns x 128 rows) and from B's first row (K rows x ldb)
   if (K * ldb * (int64_t)sizeof(float) >= ((int64_t)1 << 31) ||
       K * 128 * (int64_t)sizeof(float) >= ((int64_t)1 << 31))
     return fail_arg("nn_kernel: K x ldb too large for 32-bit buffer offsets (split the columns)");
-  if (cols % 512 == 0)
-    return launch_nn<4>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s, gate);
-  if (cols % 256 == 0)
-    return launch_nn<2>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s, gate);
-  return launch_nn<1>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s, gate);
-}
-
-// nn_gemm's exp form with the IMQ staging K = u^pw (the exact f32 engine)
-static int nn_gemm_imq(const float* A, int64_t K, const float* B, int64_t ldb, int64_t cols,
-                       int splits, const dsvgd_select_state* st, float* C, int64_t ldc,
-                       float* rowsum, int64_t m, int64_t row0, hipStream_t s, const float* gate,
-                       float pw) {
-  if (K * ldb * (int64_t)sizeof(float) >= ((int64_t)1 << 31) ||
-      K * 128 * (int64_t)sizeof(float) >= ((int64_t)1 << 31))
-    return fail_arg("nn_kernel: K x ldb too large for 32-bit buffer offsets (split the columns)");
-  if (cols % 512 == 0)
-    return launch_nn<4, kFamIMQ>(true, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s,
-                                 gate, pw);
-  if (cols % 256 == 0)
-    return launch_nn<2, kFamIMQ>(true, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s,
-                                 gate, pw);
-  return launch_nn<1, kFamIMQ>(true, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, row0, s,
-                               gate, pw);
+  if (fam == kFamIMQ && !exp_) return fail_arg("nn_kernel: the IMQ staging is the exp form's");
+#define DSVGD_NN_TN(TN)                                                                          \
+  return fam == kFamIMQ ? launch_nn<TN, kFamIMQ>(true, A, B, ldb, K, splits, st, C, ldc, rowsum, \
+                                                 m, cols, row0, s, gate, pw)                     \
+                        : launch_nn<TN>(exp_, A, B, ldb, K, splits, st, C, ldc, rowsum, m, cols, \
+                                        row0, s, gate)
+  if (cols % 512 == 0) DSVGD_NN_TN(4);
+  if (cols % 256 == 0) DSVGD_NN_TN(2);
+  DSVGD_NN_TN(1);
+#undef DSVGD_NN_TN
 }
 
 // split-K slices: (1) enough for >= 2 blocks per CU (256 CUs) when the owned
@@ -1308,36 +1288,61 @@ int dsvgd_phi_set_symrow(int on) {
   return prev;
 }
 
-int dsvgd_phi_mm(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
-                 int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KY,
-                 int64_t ldk, float* rowsum, void* stream) {
-  DSVGD_REQUIRE(D && Y && st && KY && rowsum, "null pointer");
+// ---- phi_mm: one implementation per engine --------------------------------
+// The plain names pass the RBF description on; IMQ: the u^pw staging with pw
+// = beta (order 0: F) or beta - 1 (order 1: G').
+#define DSVGD_REQUIRE_KERN(kern, order)                                                       \
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");              \
+  DSVGD_REQUIRE((order) == 0 || ((order) == 1 && (kern).family == DSVGD_KERNEL_IMQ),          \
+                "order: 0, or 1 (the gradient's matrix G') for the IMQ family")
+
+// The checks every phi_mm entry point shares, after its kernel description's:
+// `ptrs` (the caller's pointers, all non-null), the sizes, D's panel layout,
+// the B operand's leading dimension ldb (w: the one-operand form's dp), the
+// alignment, the grid limits and the row block.  0 (ldd is then n_pad), or
+// the error code.
+static int phi_mm_check(bool ptrs, const void* D, const void* B, int64_t ldd, int64_t ldb,
+                        int64_t ldk, int64_t row0, int64_t m, int64_t n, int64_t splits,
+                        bool w = false) {
+  DSVGD_REQUIRE(ptrs, "null pointer");
   DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
-  const int64_t n_pad = roundup(n, 128);
-  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
-  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
-  DSVGD_REQUIRE(((uintptr_t)Y & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
+  DSVGD_REQUIRE(ldd == roundup(n, 128), "ldd must equal roundup(n,128) (panel layout)");
+  if (w)
+    DSVGD_REQUIRE(ldb > 0 && ldb % 256 == 0 && ldk >= ldb,
+                  "ldw (= dp) must be a multiple of 256, ldk >= ldw");
+  else
+    DSVGD_REQUIRE(ldb % 128 == 0 && ldk >= ldb, "ldy must be a multiple of 128, ldk >= ldy");
+  DSVGD_REQUIRE(((uintptr_t)B & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
   DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
   DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
   DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
-  return nn_gemm(true, D, n_pad, Y, ldy, ldy, (int)splits, st, KY, ldk, rowsum, m, row0,
-                 (hipStream_t)stream, nullptr);
+  return 0;
+}
+
+int dsvgd_phi_mm_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                      int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
+                      float* KY, int64_t ldk, float* rowsum, const float* gate,
+                      dsvgd_kernel kern, int order, void* stream) {
+  DSVGD_REQUIRE_KERN(kern, order);
+  if (int rc = phi_mm_check(D && Y && st && KY && rowsum, D, Y, ldd, ldy, ldk, row0, m, n, splits))
+    return rc;
+  return nn_gemm(true, D, ldd, Y, ldy, ldy, (int)splits, st, KY, ldk, rowsum, m, row0,
+                 (hipStream_t)stream, gate, kern.family, kern.beta - (float)order);
+}
+
+int dsvgd_phi_mm(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                 int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KY,
+                 int64_t ldk, float* rowsum, void* stream) {
+  return dsvgd_phi_mm_kern(D, ldd, Y, ldy, row0, m, n, st, splits, KY, ldk, rowsum, nullptr,
+                           kRbfKern, 0, stream);
 }
 
 int dsvgd_phi_mm_gated(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
                        int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
                        float* KY, int64_t ldk, float* rowsum, const float* gate, void* stream) {
-  DSVGD_REQUIRE(D && Y && st && KY && rowsum && gate, "null pointer");
-  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
-  const int64_t n_pad = roundup(n, 128);
-  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
-  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
-  DSVGD_REQUIRE(((uintptr_t)Y & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
-  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
-  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
-  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
-  return nn_gemm(true, D, n_pad, Y, ldy, ldy, (int)splits, st, KY, ldk, rowsum, m, row0,
-                 (hipStream_t)stream, gate);
+  DSVGD_REQUIRE(gate, "null pointer");
+  return dsvgd_phi_mm_kern(D, ldd, Y, ldy, row0, m, n, st, splits, KY, ldk, rowsum, gate, kRbfKern,
+                           0, stream);
 }
 
 int64_t dsvgd_ysplit_bytes(int64_t rows, int64_t ldy) {
@@ -1373,105 +1378,29 @@ int dsvgd_rowsplit(const float* A, int64_t lda, int64_t rows, int64_t cols, int6
   return check_launch("rowsplit");
 }
 
-int dsvgd_phi_mm_x3(const float* D, int64_t ldd, const void* Yx, int64_t ldy, int64_t row0,
-                    int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KY,
-                    int64_t ldk, float* rowsum, int sym, int m16, const float* gate,
-                    void* stream) {
-  DSVGD_REQUIRE(D && Yx && st && KY && rowsum, "null pointer");
-  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
-  const int64_t n_pad = roundup(n, 128);
-  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
-  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
-  DSVGD_REQUIRE(((uintptr_t)Yx & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
-  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
-  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
-  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
-  // buffer-resource loads: 32-bit byte offsets into the block's D panel row
-  // and into Yx (K rows x 3 parts x ldy x 2 B)
-  DSVGD_REQUIRE(n_pad * ldy * 6 < ((int64_t)1 << 31) && n_pad * 128 * 4 < ((int64_t)1 << 31),
-                "n x ldy too large for 32-bit buffer offsets (use dsvgd_phi_mm)");
-  DSVGD_REQUIRE(!sym || (m == n && row0 == 0), "sym: the symmetric layout needs m == n, row0 == 0");
-  return nn_x3_gemm(true, D, n_pad, (const __bf16*)Yx, ldy, (int)splits, st, KY, ldk, rowsum, m,
-                    row0, (hipStream_t)stream, sym, m16, gate);
-}
-
-int dsvgd_phi_mm_h2(const float* D, int64_t ldd, const void* Yh, int64_t ldy, int64_t row0,
-                    int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KY,
-                    int64_t ldk, float* rowsum, int sym, const float* colinv, const float* gate,
-                    void* stream) {
-  DSVGD_REQUIRE(D && Yh && st && KY && rowsum && colinv, "null pointer");
-  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
-  const int64_t n_pad = roundup(n, 128);
-  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
-  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
-  DSVGD_REQUIRE(((uintptr_t)Yh & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
-  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
-  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
-  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
-  DSVGD_REQUIRE(n_pad * ldy * 4 < ((int64_t)1 << 31) && n_pad * 128 * 4 < ((int64_t)1 << 31),
-                "n x ldy too large for 32-bit buffer offsets (use dsvgd_phi_mm)");
-  DSVGD_REQUIRE(!sym || (m == n && row0 == 0 && ldy % 256 == 0),
-                "sym: the symmetric layout needs m == n, row0 == 0, ldy % 256 == 0");
-  return nn_h2_gemm(true, D, n_pad, (const _Float16*)Yh, ldy, (int)splits, st, KY, ldk, rowsum, m,
-                    row0, (hipStream_t)stream, sym, colinv, gate);
-}
-
-// ---- phi_mm with a kernel description (include/dsvgd.h) -------------------
-// RBF: the entry point beside it; IMQ: the same checks, the u^pw staging with
-// pw = beta (order 0: F) or beta - 1 (order 1: G').
-static bool kern_ok(dsvgd_kernel k) {
-  return k.family == DSVGD_KERNEL_RBF ||
-         (k.family == DSVGD_KERNEL_IMQ && k.beta >= -1.f && k.beta < 0.f);
-}
-#define DSVGD_REQUIRE_KERN(kern, order)                                                       \
-  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");              \
-  DSVGD_REQUIRE((order) == 0 || ((order) == 1 && (kern).family == DSVGD_KERNEL_IMQ),          \
-                "order: 0, or 1 (the gradient's matrix G') for the IMQ family")
-
-int dsvgd_phi_mm_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
-                      int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
-                      float* KY, int64_t ldk, float* rowsum, const float* gate,
-                      dsvgd_kernel kern, int order, void* stream) {
-  DSVGD_REQUIRE_KERN(kern, order);
-  if (kern.family == DSVGD_KERNEL_RBF)
-    return gate ? dsvgd_phi_mm_gated(D, ldd, Y, ldy, row0, m, n, st, splits, KY, ldk, rowsum, gate,
-                                     stream)
-                : dsvgd_phi_mm(D, ldd, Y, ldy, row0, m, n, st, splits, KY, ldk, rowsum, stream);
-  DSVGD_REQUIRE(D && Y && st && KY && rowsum, "null pointer");
-  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
-  const int64_t n_pad = roundup(n, 128);
-  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
-  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
-  DSVGD_REQUIRE(((uintptr_t)Y & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
-  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
-  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
-  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
-  return nn_gemm_imq(D, n_pad, Y, ldy, ldy, (int)splits, st, KY, ldk, rowsum, m, row0,
-                     (hipStream_t)stream, gate, kern.beta - (float)order);
-}
-
 int dsvgd_phi_mm_x3_kern(const float* D, int64_t ldd, const void* Yx, int64_t ldy, int64_t row0,
                          int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits,
                          float* KY, int64_t ldk, float* rowsum, int sym, int m16,
                          const float* gate, dsvgd_kernel kern, int order, void* stream) {
   DSVGD_REQUIRE_KERN(kern, order);
-  if (kern.family == DSVGD_KERNEL_RBF)
-    return dsvgd_phi_mm_x3(D, ldd, Yx, ldy, row0, m, n, st, splits, KY, ldk, rowsum, sym, m16, gate,
-                           stream);
-  DSVGD_REQUIRE(D && Yx && st && KY && rowsum, "null pointer");
-  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
-  const int64_t n_pad = roundup(n, 128);
-  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
-  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
-  DSVGD_REQUIRE(((uintptr_t)Yx & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
-  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
-  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
-  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
-  DSVGD_REQUIRE(n_pad * ldy * 6 < ((int64_t)1 << 31) && n_pad * 128 * 4 < ((int64_t)1 << 31),
+  if (int rc = phi_mm_check(D && Yx && st && KY && rowsum, D, Yx, ldd, ldy, ldk, row0, m, n,
+                            splits))
+    return rc;
+  // buffer-resource loads: 32-bit byte offsets into the block's D panel row
+  // and into Yx (K rows x 3 parts x ldy x 2 B)
+  DSVGD_REQUIRE(ldd * ldy * 6 < ((int64_t)1 << 31) && ldd * 128 * 4 < ((int64_t)1 << 31),
                 "n x ldy too large for 32-bit buffer offsets (use dsvgd_phi_mm_kern)");
   DSVGD_REQUIRE(!sym || (m == n && row0 == 0), "sym: the symmetric layout needs m == n, row0 == 0");
-  return nn_x3_gemm_imq(D, n_pad, (const __bf16*)Yx, ldy, (int)splits, st, KY, ldk, rowsum, m, row0,
-                        (hipStream_t)stream, sym, m16, gate, kern.beta - (float)order);
+  return nn_x3_gemm(true, D, ldd, (const __bf16*)Yx, ldy, (int)splits, st, KY, ldk, rowsum, m, row0,
+                    (hipStream_t)stream, sym, m16, gate, kern.family, kern.beta - (float)order);
+}
+
+int dsvgd_phi_mm_x3(const float* D, int64_t ldd, const void* Yx, int64_t ldy, int64_t row0,
+                    int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KY,
+                    int64_t ldk, float* rowsum, int sym, int m16, const float* gate,
+                    void* stream) {
+  return dsvgd_phi_mm_x3_kern(D, ldd, Yx, ldy, row0, m, n, st, splits, KY, ldk, rowsum, sym, m16,
+                              gate, kRbfKern, 0, stream);
 }
 
 int dsvgd_phi_mm_h2_kern(const float* D, int64_t ldd, const void* Yh, int64_t ldy, int64_t row0,
@@ -1479,44 +1408,37 @@ int dsvgd_phi_mm_h2_kern(const float* D, int64_t ldd, const void* Yh, int64_t ld
                          float* KY, int64_t ldk, float* rowsum, int sym, const float* colinv,
                          const float* gate, dsvgd_kernel kern, int order, void* stream) {
   DSVGD_REQUIRE_KERN(kern, order);
-  if (kern.family == DSVGD_KERNEL_RBF)
-    return dsvgd_phi_mm_h2(D, ldd, Yh, ldy, row0, m, n, st, splits, KY, ldk, rowsum, sym, colinv,
-                           gate, stream);
-  DSVGD_REQUIRE(D && Yh && st && KY && rowsum && colinv, "null pointer");
-  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
-  const int64_t n_pad = roundup(n, 128);
-  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
-  DSVGD_REQUIRE(ldy % 128 == 0 && ldk >= ldy, "ldy must be a multiple of 128, ldk >= ldy");
-  DSVGD_REQUIRE(((uintptr_t)Yh & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
-  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
-  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
-  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
-  DSVGD_REQUIRE(n_pad * ldy * 4 < ((int64_t)1 << 31) && n_pad * 128 * 4 < ((int64_t)1 << 31),
+  if (int rc = phi_mm_check(D && Yh && st && KY && rowsum && colinv, D, Yh, ldd, ldy, ldk, row0, m,
+                            n, splits))
+    return rc;
+  DSVGD_REQUIRE(ldd * ldy * 4 < ((int64_t)1 << 31) && ldd * 128 * 4 < ((int64_t)1 << 31),
                 "n x ldy too large for 32-bit buffer offsets (use dsvgd_phi_mm_kern)");
   DSVGD_REQUIRE(!sym || (m == n && row0 == 0 && ldy % 256 == 0),
                 "sym: the symmetric layout needs m == n, row0 == 0, ldy % 256 == 0");
-  return nn_h2_gemm_imq(D, n_pad, (const _Float16*)Yh, ldy, (int)splits, st, KY, ldk, rowsum, m,
-                        row0, (hipStream_t)stream, sym, colinv, gate, kern.beta - (float)order);
+  return nn_h2_gemm(true, D, ldd, (const _Float16*)Yh, ldy, (int)splits, st, KY, ldk, rowsum, m,
+                    row0, (hipStream_t)stream, sym, colinv, gate, kern.family,
+                    kern.beta - (float)order);
+}
+
+int dsvgd_phi_mm_h2(const float* D, int64_t ldd, const void* Yh, int64_t ldy, int64_t row0,
+                    int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KY,
+                    int64_t ldk, float* rowsum, int sym, const float* colinv, const float* gate,
+                    void* stream) {
+  return dsvgd_phi_mm_h2_kern(D, ldd, Yh, ldy, row0, m, n, st, splits, KY, ldk, rowsum, sym,
+                              colinv, gate, kRbfKern, 0, stream);
 }
 
 int dsvgd_phi_mm_h2w(const float* D, int64_t ldd, const void* Wh, int64_t ldw, int64_t row0,
                      int64_t m, int64_t n, const dsvgd_select_state* st, int64_t splits, float* KW,
                      int64_t ldk, float* rowsum, int sym, const float* colinv, const float* gate,
                      void* stream) {
-  DSVGD_REQUIRE(D && Wh && st && KW && rowsum && colinv, "null pointer");
-  DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
-  const int64_t n_pad = roundup(n, 128);
-  DSVGD_REQUIRE(ldd == n_pad, "ldd must equal roundup(n,128) (panel layout)");
-  DSVGD_REQUIRE(ldw > 0 && ldw % 256 == 0 && ldk >= ldw,
-                "ldw (= dp) must be a multiple of 256, ldk >= ldw");
-  DSVGD_REQUIRE(((uintptr_t)Wh & 15) == 0 && ((uintptr_t)D & 15) == 0, "16-byte alignment");
-  DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
-  DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
-  DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
-  DSVGD_REQUIRE(n_pad * ldw * 4 < ((int64_t)1 << 31) && n_pad * 128 * 4 < ((int64_t)1 << 31),
+  if (int rc = phi_mm_check(D && Wh && st && KW && rowsum && colinv, D, Wh, ldd, ldw, ldk, row0, m,
+                            n, splits, true))
+    return rc;
+  DSVGD_REQUIRE(ldd * ldw * 4 < ((int64_t)1 << 31) && ldd * 128 * 4 < ((int64_t)1 << 31),
                 "n x ldw too large for 32-bit buffer offsets");
   DSVGD_REQUIRE(!sym || (m == n && row0 == 0), "sym: the symmetric layout needs m == n, row0 == 0");
-  return nn_h2w_gemm(D, n_pad, (const _Float16*)Wh, ldw, (int)splits, st, KW, ldk, rowsum, m, row0,
+  return nn_h2w_gemm(D, ldd, (const _Float16*)Wh, ldw, (int)splits, st, KW, ldk, rowsum, m, row0,
                      (hipStream_t)stream, sym, colinv, gate);
 }
 
@@ -1785,11 +1707,12 @@ int dsvgd_phi_finish_imq(const float* KF, int64_t ldkf, const float* KG, int64_t
   return check_launch("phi_finish_imq");
 }
 
-static int phi_direct_impl(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
-                           int64_t m, int64_t n, int64_t d, const dsvgd_select_state* st,
-                           float inv_n, float step, const float* extra, int64_t lde, float* phi,
-                           int64_t ldphi, float* X, int64_t ldx, float* partial,
-                           int64_t partial_floats, dsvgd_kernel kern, void* stream) {
+int dsvgd_phi_direct_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
+                          int64_t m, int64_t n, int64_t d, const dsvgd_select_state* st,
+                          float inv_n, float step, const float* extra, int64_t lde, float* phi,
+                          int64_t ldphi, float* X, int64_t ldx, float* partial,
+                          int64_t partial_floats, dsvgd_kernel kern, void* stream) {
+  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
   DSVGD_REQUIRE(D && Y && st, "null pointer");
   DSVGD_REQUIRE(!extra || lde >= d, "lde");
   DSVGD_REQUIRE(m > 0 && n > 0 && d > 0 && row0 >= 0, "sizes");
@@ -1833,45 +1756,36 @@ int dsvgd_phi_direct(const float* D, int64_t ldd, const float* Y, int64_t ldy, i
                      float step, const float* extra, int64_t lde, float* phi, int64_t ldphi,
                      float* X, int64_t ldx, float* partial, int64_t partial_floats,
                      void* stream) {
-  return phi_direct_impl(D, ldd, Y, ldy, row0, m, n, d, st, inv_n, step, extra, lde, phi, ldphi, X,
-                         ldx, partial, partial_floats, dsvgd_kernel{DSVGD_KERNEL_RBF, 0.f}, stream);
+  return dsvgd_phi_direct_kern(D, ldd, Y, ldy, row0, m, n, d, st, inv_n, step, extra, lde, phi,
+                               ldphi, X, ldx, partial, partial_floats, kRbfKern, stream);
 }
 
-int dsvgd_phi_direct_kern(const float* D, int64_t ldd, const float* Y, int64_t ldy, int64_t row0,
-                          int64_t m, int64_t n, int64_t d, const dsvgd_select_state* st,
-                          float inv_n, float step, const float* extra, int64_t lde, float* phi,
-                          int64_t ldphi, float* X, int64_t ldx, float* partial,
-                          int64_t partial_floats, dsvgd_kernel kern, void* stream) {
+// (LDS, 64 KiB: 2 d floats and two arrays of 256; the IMQ's second
+// coefficient is a third array, so its d limit is 128 lower)
+int dsvgd_phi_row_kern(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n_int,
+                       int64_t d, int64_t i, const dsvgd_select_state* st, float step,
+                       const float* extra, float* phi_out, dsvgd_kernel kern, void* stream) {
   DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
-  return phi_direct_impl(D, ldd, Y, ldy, row0, m, n, d, st, inv_n, step, extra, lde, phi, ldphi, X,
-                         ldx, partial, partial_floats, kern, stream);
+  const bool imq = kern.family == DSVGD_KERNEL_IMQ;
+  DSVGD_REQUIRE(X && S && st, "null pointer");
+  DSVGD_REQUIRE(n_int > 0 && d > 0 && i >= 0 && i < n_int && ldx >= d && lds >= d, "sizes");
+  DSVGD_REQUIRE(d <= (imq ? 7808 : 7936), imq ? "phi_row (IMQ) supports d <= 7808 (64 KiB LDS)"
+                                              : "phi_row supports d <= 7936 (64 KiB LDS)");
+  const size_t shm = (size_t)(2 * d + (imq ? 768 : 512)) * sizeof(float);
+  if (imq)
+    hipLaunchKernelGGL(phi_row_kernel<kFamIMQ>, dim3(1), dim3(256), shm, (hipStream_t)stream, X,
+                       ldx, S, lds, n_int, d, i, st, step, extra, phi_out, kern.beta);
+  else
+    hipLaunchKernelGGL(phi_row_kernel<kFamRBF>, dim3(1), dim3(256), shm, (hipStream_t)stream, X,
+                       ldx, S, lds, n_int, d, i, st, step, extra, phi_out, 0.f);
+  return check_launch("phi_row");
 }
 
 int dsvgd_phi_row(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n_int, int64_t d,
                   int64_t i, const dsvgd_select_state* st, float step, const float* extra,
                   float* phi_out, void* stream) {
-  DSVGD_REQUIRE(X && S && st, "null pointer");
-  DSVGD_REQUIRE(n_int > 0 && d > 0 && i >= 0 && i < n_int && ldx >= d && lds >= d, "sizes");
-  DSVGD_REQUIRE(d <= 7936, "phi_row supports d <= 7936 (64 KiB LDS)");
-  const size_t shm = (size_t)(2 * d + 512) * sizeof(float);
-  hipLaunchKernelGGL(phi_row_kernel<kFamRBF>, dim3(1), dim3(256), shm, (hipStream_t)stream, X, ldx,
-                     S, lds, n_int, d, i, st, step, extra, phi_out, 0.f);
-  return check_launch("phi_row");
-}
-
-int dsvgd_phi_row_kern(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n_int,
-                       int64_t d, int64_t i, const dsvgd_select_state* st, float step,
-                       const float* extra, float* phi_out, dsvgd_kernel kern, void* stream) {
-  DSVGD_REQUIRE(kern_ok(kern), "kern: family RBF, or IMQ with beta in [-1, 0)");
-  if (kern.family == DSVGD_KERNEL_RBF)
-    return dsvgd_phi_row(X, ldx, S, lds, n_int, d, i, st, step, extra, phi_out, stream);
-  DSVGD_REQUIRE(X && S && st, "null pointer");
-  DSVGD_REQUIRE(n_int > 0 && d > 0 && i >= 0 && i < n_int && ldx >= d && lds >= d, "sizes");
-  DSVGD_REQUIRE(d <= 7808, "phi_row (IMQ) supports d <= 7808 (64 KiB LDS)");
-  const size_t shm = (size_t)(2 * d + 768) * sizeof(float);
-  hipLaunchKernelGGL(phi_row_kernel<kFamIMQ>, dim3(1), dim3(256), shm, (hipStream_t)stream, X, ldx,
-                     S, lds, n_int, d, i, st, step, extra, phi_out, kern.beta);
-  return check_launch("phi_row(imq)");
+  return dsvgd_phi_row_kern(X, ldx, S, lds, n_int, d, i, st, step, extra, phi_out, kRbfKern,
+                            stream);
 }
 
 int64_t dsvgd_phi_row_blocks(int64_t n, int64_t d) {
@@ -1885,7 +1799,7 @@ int dsvgd_phi_row_split(float* X, int64_t ldx, const float* S, int64_t lds, int6
                         int64_t i, const dsvgd_select_state* st, float step, const float* extra,
                         float* phi_out, float* partial, int64_t blocks, void* stream) {
   return dsvgd_phi_row_split_kern(X, ldx, S, lds, n, d, i, st, step, extra, phi_out, partial,
-                                  blocks, dsvgd_kernel{DSVGD_KERNEL_RBF, 0.f}, stream);
+                                  blocks, kRbfKern, stream);
 }
 
 int dsvgd_phi_row_split_kern(float* X, int64_t ldx, const float* S, int64_t lds, int64_t n,

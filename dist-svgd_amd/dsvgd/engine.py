@@ -592,23 +592,16 @@ class PhiEngine(object):
         if self.d <= self.DIRECT_MAX_D:
             with span(self.timer, "phi_direct"):
                 # KY (the MFMA path's split-K buffer) doubles as the split-J scratch
-                if self.imq:
-                    N.call("dsvgd_phi_direct_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y),
-                           self.ldy, self.row0, self.m, self.n, self.d, self.state.ptr,
-                           float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx,
-                           N.ptr(self.KY), self.KY.numel(), self._kern, s)
-                    return
-                N.call("dsvgd_phi_direct", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
-                       self.row0, self.m, self.n, self.d, self.state.ptr, float(inv_n),
-                       float(step), ex, lde, phi, self.d, xo, ldx, N.ptr(self.KY),
-                       self.KY.numel(), s)
-            return
-        if self.imq:
-            self._direction_imq(inv_n, step, ex, lde, phi, xo, ldx, s)
+                N.call("dsvgd_phi_direct_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y),
+                       self.ldy, self.row0, self.m, self.n, self.d, self.state.ptr,
+                       float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx,
+                       N.ptr(self.KY), self.KY.numel(), self._kern, s)
             return
         if self.phi_form == "w":
             self._direction_w(inv_n, step, ex, lde, phi, xo, ldx, s)
             return
+        # The two-operand form, K . [Xc | S] once per product run (_runs: the
+        # IMQ's F . Xc is computed and not used; DESIGN.md, "The IMQ kernel")
         if self.sym and self.phi_gemm == "h2":
             # the slices were sized for the symmetric phi_mm form in force at
             # construction (dsvgd_phi_splits_sym: longer slices for the
@@ -621,51 +614,52 @@ class PhiEngine(object):
                                       device=self.device)
                 self.rowsum = torch.empty(want * self.m_pad, dtype=torch.float32,
                                           device=self.device)
+                if self.imq:
+                    self.KY2 = torch.empty_like(self.KY)
+                    self.rowsum2 = torch.empty_like(self.rowsum)
         if self.phi_gemm == "h2":
             # the range guard word of the scales: phi_mm_h2 runs while it
-            # reads 0; otherwise the FmtX3 image and phi_mm_x3 behind it do,
-            # or (no FmtX3 image fits) the exact f32 phi_mm (all stay on the
+            # reads 0; otherwise the fallback behind it does (all stay on the
             # stream -- no host round trip)
             guard = N.ptr(self.yscale) + 4 * (2 * self.ldy + 2)
             with span(self.timer, "ysplit"):
                 self._scales(self.ldy, self.yscale, s)
                 N.call("dsvgd_h2_ysplit", N.ptr(self.Y), self.ldy, self.n_pad,
                        N.ptr(self.yscale), N.ptr(self.Yx), s)
-            with span(self.timer, "phi_mm"):
-                N.call("dsvgd_phi_mm_h2", N.ptr(self.D), self.n_pad, N.ptr(self.Yx), self.ldy,
-                       self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(self.KY),
-                       self.ldy, N.ptr(self.rowsum), int(self.sym),
-                       N.ptr(self.yscale) + 4 * self.ldy, guard, s)
-            if self.Yx3 is None:
-                with span(self.timer, "phi_guard"):
-                    N.call("dsvgd_phi_mm_gated", N.ptr(self.D), self.n_pad, N.ptr(self.Y),
+            for order, KY, rs, name in self._runs():
+                with span(self.timer, name):
+                    N.call("dsvgd_phi_mm_h2_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Yx),
                            self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
-                           N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), guard, s)
-            else:
-                with span(self.timer, "phi_guard"):
-                    N.call("dsvgd_ysplit", N.ptr(self.Y), self.ldy, self.n_pad, N.ptr(self.Yx3),
-                           0 if self.m16_fb else 1, guard, s)
-                    N.call("dsvgd_phi_mm_x3", N.ptr(self.D), self.n_pad, N.ptr(self.Yx3),
-                           self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
-                           N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), int(self.sym),
-                           int(self.m16_fb), guard, s)
+                           N.ptr(KY), self.ldy, N.ptr(rs), int(self.sym),
+                           N.ptr(self.yscale) + 4 * self.ldy, guard, self._kern, order, s)
+            with span(self.timer, "phi_guard"):
+                self._fallback(guard, s, self.splits)
         elif self.x3:
             m16 = self.m16
             with span(self.timer, "ysplit"):
                 N.call("dsvgd_ysplit", N.ptr(self.Y), self.ldy, self.n_pad, N.ptr(self.Yx),
                        0 if m16 else 1, None, s)
-            with span(self.timer, "phi_mm"):
-                N.call("dsvgd_phi_mm_x3", N.ptr(self.D), self.n_pad, N.ptr(self.Yx), self.ldy,
-                       self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(self.KY),
-                       self.ldy, N.ptr(self.rowsum), int(self.sym), int(m16), None, s)
+            for order, KY, rs, name in self._runs():
+                with span(self.timer, name):
+                    N.call("dsvgd_phi_mm_x3_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Yx),
+                           self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
+                           N.ptr(KY), self.ldy, N.ptr(rs), int(self.sym), int(m16), None,
+                           self._kern, order, s)
         else:
-            with span(self.timer, "phi_mm"):
-                N.call("dsvgd_phi_mm", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
-                       self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(self.KY),
-                       self.ldy, N.ptr(self.rowsum), s)
-        N.call("dsvgd_phi_finish", N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), self.splits,
-               N.ptr(self.Y), self.ldy, self.row0, self.m, self.d, self.dp, self.state.ptr,
-               float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx, s)
+            for order, KY, rs, name in self._runs():
+                with span(self.timer, name):
+                    N.call("dsvgd_phi_mm_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
+                           self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(KY),
+                           self.ldy, N.ptr(rs), None, self._kern, order, s)
+        if self.imq:
+            N.call("dsvgd_phi_finish_imq", N.ptr(self.KY), self.ldy, N.ptr(self.KY2), self.ldy,
+                   N.ptr(self.rowsum2), self.splits, N.ptr(self.Y), self.ldy, self.row0, self.m,
+                   self.d, self.dp, self.state.ptr, self._kern, float(inv_n), float(step), ex,
+                   lde, phi, self.d, xo, ldx, s)
+        else:
+            N.call("dsvgd_phi_finish", N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), self.splits,
+                   N.ptr(self.Y), self.ldy, self.row0, self.m, self.d, self.dp, self.state.ptr,
+                   float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx, s)
 
     def adagrad_direction(self, X_own, step, rule, state, inv_n=None, extra=None, p2p=None):
         """The AdaGrad-conditioned step (dsvgd.adagrad) of the owned rows:
@@ -683,79 +677,33 @@ class PhiEngine(object):
                    N.ld(self.phi), N.ptr(state.G), N.ld(state.G), self.m, self.d, float(step),
                    float(rule.alpha), float(rule.eps), N.stream(self.device))
 
-    # ------------------------------------------------------------- IMQ --
-    def _imq_runs(self):
-        """(order, KY, rowsum, span name) of the two products: F = u^beta
-        into KY / rowsum, G' = u^(beta-1) into KY2 / rowsum2."""
+    # ------------------------------------------- product runs, fallback --
+    def _runs(self):
+        """(order, KY, rowsum, span name) of the two-operand phi_mm's product
+        runs.  RBF: K into KY / rowsum.  IMQ: F = u^beta into KY / rowsum and
+        G' = u^(beta-1) into KY2 / rowsum2."""
+        if not self.imq:
+            return ((0, self.KY, self.rowsum, "phi_mm"),)
         return ((0, self.KY, self.rowsum, "phi_mm_f"), (1, self.KY2, self.rowsum2, "phi_mm_g"))
 
-    def _imq_fallback(self, gate, s):
-        """Both products again on the FmtH2 engine's fallback (the FmtX3
+    def _fallback(self, gate, s, splits):
+        """Every product run again on the FmtH2 engine's fallback (the FmtX3
         image and phi_mm_x3, or the exact f32 phi_mm where no FmtX3 image
-        fits), gated on the device word `gate`: nothing runs while it reads
-        0.  The range guard of direction() and the gate of ksd()."""
+        fits), with `splits` slices, gated on the device word `gate`: nothing
+        runs while it reads 0.  The range guard of direction() and the gate of
+        ksd()."""
         if self.Yx3 is None:
-            for order, KY, rs, _ in self._imq_runs():
+            for order, KY, rs, _ in self._runs():
                 N.call("dsvgd_phi_mm_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
-                       self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(KY),
-                       self.ldy, N.ptr(rs), gate, self._kern, order, s)
+                       self.row0, self.m, self.n, self.state.ptr, splits, N.ptr(KY), self.ldy,
+                       N.ptr(rs), gate, self._kern, order, s)
             return
         N.call("dsvgd_ysplit", N.ptr(self.Y), self.ldy, self.n_pad, N.ptr(self.Yx3),
                0 if self.m16_fb else 1, gate, s)
-        for order, KY, rs, _ in self._imq_runs():
+        for order, KY, rs, _ in self._runs():
             N.call("dsvgd_phi_mm_x3_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Yx3), self.ldy,
-                   self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(KY), self.ldy,
+                   self.row0, self.m, self.n, self.state.ptr, splits, N.ptr(KY), self.ldy,
                    N.ptr(rs), int(self.sym), int(self.m16_fb), gate, self._kern, order, s)
-
-    def _direction_imq(self, inv_n, step, ex, lde, phi, xo, ldx, s):
-        """phi with the IMQ kernel: the two-operand phi_mm twice on the
-        engine's MFMA path (each run its own KY / rowsum and, on FmtH2, its
-        own pass through the range guard's fallback), then phi_finish_imq.
-        F . Xc is computed and not used (DESIGN.md, "The IMQ kernel")."""
-        f32 = dict(dtype=torch.float32, device=self.device)
-        if self.sym and self.phi_gemm == "h2":
-            # (the slices follow the symmetric form in force, as direction())
-            want = int(N.load().dsvgd_phi_splits_sym(self.n, self.ldy))
-            if want != self.splits:
-                self.splits = want
-                self.KY = torch.empty(want * self.m, self.ldy, **f32)
-                self.rowsum = torch.empty(want * self.m_pad, **f32)
-                self.KY2, self.rowsum2 = torch.empty_like(self.KY), torch.empty_like(self.rowsum)
-        if self.phi_gemm == "h2":
-            guard = N.ptr(self.yscale) + 4 * (2 * self.ldy + 2)
-            with span(self.timer, "ysplit"):
-                self._scales(self.ldy, self.yscale, s)
-                N.call("dsvgd_h2_ysplit", N.ptr(self.Y), self.ldy, self.n_pad,
-                       N.ptr(self.yscale), N.ptr(self.Yx), s)
-            for order, KY, rs, name in self._imq_runs():
-                with span(self.timer, name):
-                    N.call("dsvgd_phi_mm_h2_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Yx),
-                           self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
-                           N.ptr(KY), self.ldy, N.ptr(rs), int(self.sym),
-                           N.ptr(self.yscale) + 4 * self.ldy, guard, self._kern, order, s)
-            with span(self.timer, "phi_guard"):
-                self._imq_fallback(guard, s)
-        elif self.x3:
-            m16 = self.m16
-            with span(self.timer, "ysplit"):
-                N.call("dsvgd_ysplit", N.ptr(self.Y), self.ldy, self.n_pad, N.ptr(self.Yx),
-                       0 if m16 else 1, None, s)
-            for order, KY, rs, name in self._imq_runs():
-                with span(self.timer, name):
-                    N.call("dsvgd_phi_mm_x3_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Yx),
-                           self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
-                           N.ptr(KY), self.ldy, N.ptr(rs), int(self.sym), int(m16), None,
-                           self._kern, order, s)
-        else:
-            for order, KY, rs, name in self._imq_runs():
-                with span(self.timer, name):
-                    N.call("dsvgd_phi_mm_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
-                           self.row0, self.m, self.n, self.state.ptr, self.splits, N.ptr(KY),
-                           self.ldy, N.ptr(rs), None, self._kern, order, s)
-        N.call("dsvgd_phi_finish_imq", N.ptr(self.KY), self.ldy, N.ptr(self.KY2), self.ldy,
-               N.ptr(self.rowsum2), self.splits, N.ptr(self.Y), self.ldy, self.row0, self.m,
-               self.d, self.dp, self.state.ptr, self._kern, float(inv_n), float(step), ex, lde,
-               phi, self.d, xo, ldx, s)
 
     def _direction_w(self, inv_n, step, ex, lde, phi, xo, ldx, s):
         """phi_mm in the one-operand form: the scales and the image of W =
@@ -776,16 +724,7 @@ class PhiEngine(object):
                    self.m, self.n, self.state.ptr, self.splits, N.ptr(self.KY), dp,
                    N.ptr(self.rowsum), int(self.sym), N.ptr(self.wscale) + 4 * dp, guard, s)
         with span(self.timer, "phi_guard"):
-            if self.Yx3 is None:
-                N.call("dsvgd_phi_mm_gated", N.ptr(self.D), self.n_pad, N.ptr(self.Y), ldy,
-                       self.row0, self.m, self.n, self.state.ptr, self.splits_fb, N.ptr(self.KY),
-                       ldy, N.ptr(self.rowsum), guard, s)
-            else:
-                N.call("dsvgd_ysplit", N.ptr(self.Y), ldy, self.n_pad, N.ptr(self.Yx3),
-                       0 if self.m16_fb else 1, guard, s)
-                N.call("dsvgd_phi_mm_x3", N.ptr(self.D), self.n_pad, N.ptr(self.Yx3), ldy,
-                       self.row0, self.m, self.n, self.state.ptr, self.splits_fb, N.ptr(self.KY),
-                       ldy, N.ptr(self.rowsum), int(self.sym), int(self.m16_fb), guard, s)
+            self._fallback(guard, s, self.splits_fb)
         N.call("dsvgd_phi_finish_w", N.ptr(self.KY), dp, N.ptr(self.rowsum), self.splits,
                N.ptr(self.KY), ldy, self.splits_fb, N.ptr(self.Y), ldy, self.row0, self.m, self.d,
                dp, self.state.ptr, guard, float(inv_n), float(step), ex, lde, phi, self.d, xo, ldx,
@@ -1108,55 +1047,34 @@ class PhiEngine(object):
                 N.call("dsvgd_ksd_direct_kern", N.ptr(self.Y), self.ldy, self.dp, self.d,
                        self.row0, self.m, self.n, self.state.ptr, N.ptr(W["rows"]),
                        N.ptr(W["ws"]), N.ptr(W["out"]), self._kern, s)
-        elif self.imq:
-            if self.phi_gemm == "h2":
-                # the gate reads the G' run's row sums rG (G' <= F entrywise);
-                # its fallback reruns both products
-                gate = N.ptr(W["gate"])
-                with span(self.timer, "ksd_gate"):
-                    N.call("dsvgd_ksd_gate", N.ptr(self.rowsum2), self.splits, self.m, self.n,
-                           gate, s)
-                    self._imq_fallback(gate, s)
-            with span(self.timer, "ksd_rows"):
-                N.call("dsvgd_ksd_rows_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
-                       self.dp, self.d, self.row0, self.m, self.n, self.state.ptr, sym,
-                       W["parts"], N.ptr(W["P"]), N.ptr(W["a"]), self._kern, s)
-            with span(self.timer, "ksd_finish"):
-                N.call("dsvgd_ksd_finish_imq", N.ptr(self.KY), self.ldy, N.ptr(self.KY2),
-                       self.ldy, N.ptr(self.rowsum2), self.splits, N.ptr(self.Y), self.ldy,
-                       self.dp, self.d, self.row0, self.m, self.n, self.state.ptr, self._kern,
-                       sym, W["parts"], N.ptr(W["P"]), N.ptr(W["rows"]), N.ptr(W["ws"]),
-                       N.ptr(W["out"]), s)
         else:
             if self.phi_gemm == "h2":
                 # a row whose whole kernel mass is tiny sits below the FmtH2
                 # image of K's absolute precision (include/dsvgd.h,
                 # dsvgd_ksd_gate): phi_mm again on the guard's fallback engine,
-                # gated on a device word -- nothing runs while it reads 0
+                # gated on a device word -- nothing runs while it reads 0.  The
+                # IMQ's gate reads the G' run's row sums rG (G' <= F entrywise)
                 gate = N.ptr(W["gate"])
                 with span(self.timer, "ksd_gate"):
-                    N.call("dsvgd_ksd_gate", N.ptr(self.rowsum), self.splits, self.m, self.n,
-                           gate, s)
-                    if self.Yx3 is None:
-                        N.call("dsvgd_phi_mm_gated", N.ptr(self.D), self.n_pad, N.ptr(self.Y),
-                               self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
-                               N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), gate, s)
-                    else:
-                        N.call("dsvgd_ysplit", N.ptr(self.Y), self.ldy, self.n_pad,
-                               N.ptr(self.Yx3), 0 if self.m16_fb else 1, gate, s)
-                        N.call("dsvgd_phi_mm_x3", N.ptr(self.D), self.n_pad, N.ptr(self.Yx3),
-                               self.ldy, self.row0, self.m, self.n, self.state.ptr, self.splits,
-                               N.ptr(self.KY), self.ldy, N.ptr(self.rowsum), int(sym),
-                               int(self.m16_fb), gate, s)
+                    N.call("dsvgd_ksd_gate", N.ptr(self.rowsum2 if self.imq else self.rowsum),
+                           self.splits, self.m, self.n, gate, s)
+                    self._fallback(gate, s, self.splits)
             with span(self.timer, "ksd_rows"):
-                N.call("dsvgd_ksd_rows", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
+                N.call("dsvgd_ksd_rows_kern", N.ptr(self.D), self.n_pad, N.ptr(self.Y), self.ldy,
                        self.dp, self.d, self.row0, self.m, self.n, self.state.ptr, sym,
-                       W["parts"], N.ptr(W["P"]), N.ptr(W["a"]), s)
+                       W["parts"], N.ptr(W["P"]), N.ptr(W["a"]), self._kern, s)
             with span(self.timer, "ksd_finish"):
-                N.call("dsvgd_ksd_finish", N.ptr(self.KY), self.ldy, N.ptr(self.rowsum),
-                       self.splits, N.ptr(self.Y), self.ldy, self.dp, self.d, self.row0, self.m,
-                       self.n, self.state.ptr, sym, W["parts"], N.ptr(W["P"]), N.ptr(W["rows"]),
-                       N.ptr(W["ws"]), N.ptr(W["out"]), s)
+                if self.imq:
+                    N.call("dsvgd_ksd_finish_imq", N.ptr(self.KY), self.ldy, N.ptr(self.KY2),
+                           self.ldy, N.ptr(self.rowsum2), self.splits, N.ptr(self.Y), self.ldy,
+                           self.dp, self.d, self.row0, self.m, self.n, self.state.ptr, self._kern,
+                           sym, W["parts"], N.ptr(W["P"]), N.ptr(W["rows"]), N.ptr(W["ws"]),
+                           N.ptr(W["out"]), s)
+                else:
+                    N.call("dsvgd_ksd_finish", N.ptr(self.KY), self.ldy, N.ptr(self.rowsum),
+                           self.splits, N.ptr(self.Y), self.ldy, self.dp, self.d, self.row0,
+                           self.m, self.n, self.state.ptr, sym, W["parts"], N.ptr(W["P"]),
+                           N.ptr(W["rows"]), N.ptr(W["ws"]), N.ptr(W["out"]), s)
         if out is None:
             out = W["out"].clone()
         else:

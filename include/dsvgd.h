@@ -1065,8 +1065,9 @@ int dsvgd_ksd_direct(const float* Y, int64_t ldy, int64_t dp, int64_t d, int64_t
  * u lie in (0, 1] and the +inf pads of D map to 0, as exp(-D/h) does.
  *
  * A kernel is described on the host and passed BY VALUE to the entry points
- * below, each beside the one it extends (no process-wide setting).  With the
- * RBF family each one is the call beside it. */
+ * below, each beside the one it extends (no process-wide setting).  Both
+ * names reach one implementation: the plain name is the _kern call with the
+ * RBF family (the same checks, error texts and launches). */
 #define DSVGD_KERNEL_RBF 0 /* exp(-|x - y|^2 / h); beta is ignored          */
 #define DSVGD_KERNEL_IMQ 1 /* (1 + |x - y|^2 / h)^beta, beta in [-1, 0)     */
 typedef struct dsvgd_kernel {

@@ -180,6 +180,29 @@ def test_phi_behind_the_range_guard():
     assert rel_err(phi, R.phi64(X, S, h, beta)) < PHI_TOL
 
 
+@pytest.mark.parametrize("image", [True, False])
+def test_phi_guard_fallback_both_branches(image):
+    """The same outlier on the full D layout (n = 512, ldy = 128) through the
+    fallback's two branches: both products on the FmtX3 image and, with the
+    image taken away, on the gated f32 phi_mm."""
+    n, d, beta = 512, 64, -0.5
+    rs = np.random.RandomState(3)
+    X = (0.3 * rs.randn(n, d)).astype(np.float32)
+    S = (-X / 0.09 + rs.randn(n, d)).astype(np.float32)
+    X[17, 0] += np.float32(2.0 ** 17)
+    h = 0.2 * d
+    eng = dsvgd().PhiEngine(n, d, device=DEV, kernel=dsvgd().IMQ(1.0, beta))
+    assert eng.phi_gemm == "h2" and not eng.sym and eng.Yx3 is not None
+    if not image:
+        eng.Yx3 = None
+    eng.step(gpu(X), gpu(S), h=h)
+    torch.cuda.synchronize()
+    assert eng.range_guard() is True
+    phi = eng.phi.cpu().numpy()
+    assert np.isfinite(phi).all()
+    assert rel_err(phi, R.phi64(X, S, h, beta)) < PHI_TOL
+
+
 def test_phi_direct_d2_and_extra_step():
     """d = 2 on the direct kernel, with `extra` rows and the X update."""
     n, d, beta, h, eps = 200, 2, -0.75, 0.8, 0.05
@@ -287,9 +310,12 @@ def test_sequential_sweep_row_split_kernels():
 
 
 # ------------------------------------------------------------------ KSD --
-def _ksd_run(X, S, beta, h=None, **kw):
+def _ksd_run(X, S, beta, h=None, image=True, **kw):
+    """image=False: the engine's FmtX3 fallback image taken away."""
     n, d = X.shape
     eng = dsvgd().PhiEngine(n, d, device=DEV, kernel=dsvgd().IMQ(1.0, beta), **kw)
+    if not image:
+        eng.Yx3 = None
     eng.pack(gpu(X), gpu(S))
     eng.distances(median=h is None)
     if h is None:
@@ -364,6 +390,19 @@ def test_ksd_outlier_row_trips_the_gate():
     eng, out, rows = _ksd_run(X, S, beta, h=h)
     assert float(eng._ksd["gate"][0]) == 1.0
     _ksd_check(out, rows, ref)
+
+
+def test_ksd_gate_without_an_x3_image():
+    """The gate's other branch on the same outlier: with the FmtX3 image
+    taken away both products rerun on the gated f32 phi_mm."""
+    n, d, beta = 129, 37, -0.5
+    X, S, _, _ = _problem(n, d, seed=4)
+    h = float(np.float32(sqdist64(X).mean()))
+    X = X.copy()
+    X[5] += 256.0
+    eng, out, rows = _ksd_run(X, S, beta, h=h, image=False)
+    assert not eng.sym and float(eng._ksd["gate"][0]) == 1.0
+    _ksd_check(out, rows, R.ksd_reference(X, S, h, beta))
 
 
 def test_metrics_ksd_equals_engine_path():

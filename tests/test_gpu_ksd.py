@@ -40,11 +40,14 @@ def _scores(X, target):
     return Xg, Sg
 
 
-def _run(Xg, Sg, h=None, m=None, row0=0, **kw):
-    """One engine evaluation; h=None: the median bandwidth."""
+def _run(Xg, Sg, h=None, m=None, row0=0, image=True, **kw):
+    """One engine evaluation; h=None: the median bandwidth; image=False: the
+    engine's FmtX3 fallback image taken away."""
     import dsvgd
     n, d = Xg.shape
     eng = dsvgd.PhiEngine(n, d, m=m, row0=row0, device=DEV, **kw)
+    if not image:
+        eng.Yx3 = None
     eng.pack(Xg, Sg)
     eng.distances(median=h is None)
     if h is None:
@@ -134,6 +137,19 @@ def test_ksd_outlier_row_below_the_fp16_image_of_k():
     X2, _ = _problem(n, d, seed=4)
     eng2, _, _ = _run(*_scores(X2, target))
     assert float(eng2._ksd["gate"][0]) == 0.0
+
+
+def test_ksd_gate_without_an_x3_image():
+    """The gate's other branch on the same outlier: with the FmtX3 image
+    taken away phi_mm reruns on the gated f32 engine."""
+    n, d = 129, 37
+    X, target = _problem(n, d, seed=4)
+    X[5] += 8.0
+    Xg, Sg = _scores(X, target)
+    h = float(np.float32(sqdist64(X).mean()))
+    eng, out, rows = _run(Xg, Sg, h=h, image=False)
+    assert not eng.sym and float(eng._ksd["gate"][0]) == 1.0
+    _check(out, rows, ksd_reference(X, Sg.cpu().numpy(), h))
 
 
 def test_ksd_direct_gmm_1d():

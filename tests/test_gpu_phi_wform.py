@@ -240,6 +240,27 @@ def test_outlier_rows_and_guard_fallback(kind, k):
         assert torch.equal(eng.rowsum[:nr], eng3.rowsum)
 
 
+@pytest.mark.parametrize("image", [True, False])
+def test_guard_fallback_of_a_row_block(image):
+    """The guard's two fallback branches at a small shape: a row block (the
+    full D layout) of a "w" engine with one score row 2^20 larger, on the
+    FmtX3 image and, with the image taken away, on the gated f32 phi_mm
+    (both with the fallback's own slice count): every row within ROW_TOL."""
+    n, d, m, row0 = 512, 256, 256, 128
+    X, S = _outlier_case(n, d, "score", 20)
+    eng = dsvgd().PhiEngine(n, d, m=m, row0=row0, device=DEV, phi_form="w")
+    assert eng.phi_form == "w" and not eng.sym and eng.Yx3 is not None
+    if not image:
+        eng.Yx3 = None
+    h = 2.0 * d * 0.09
+    eng.step(gpu(X), gpu(S), X_own=gpu(X[row0:row0 + m]).clone(), step=0.0, h=h)
+    torch.cuda.synchronize()
+    assert eng.range_guard() is True
+    e = row_err(eng.phi.cpu().numpy(), O.phi(X, S, h, rows=np.arange(row0, row0 + m)))
+    record_parity(float(e.max()), image=image)
+    assert e.max() <= ROW_TOL, (e.max(), int(e.argmax()))
+
+
 # -------------------------------------------------------- 5. engagement --
 def test_form_engages_only_where_it_applies():
     E = dsvgd().PhiEngine

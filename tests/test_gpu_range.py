@@ -116,6 +116,28 @@ def test_guard_path_is_the_x3_phi_mm():
     assert torch.equal(eng.KY, eng3.KY) and torch.equal(eng.rowsum, eng3.rowsum)
 
 
+def test_guard_path_without_an_x3_image_is_the_f32_phi_mm():
+    """The guard's other branch at a small shape: an engine on the full D
+    layout (ldy = 128) with its FmtX3 image taken away runs the gated f32
+    phi_mm, so KY and the row sums are bit for bit the f32 engine's on the
+    same D (one slice each) and every row meets the bound."""
+    n, d = 512, 64
+    X, S = _outlier_case(n, d, "score", 20)
+    eng = dsvgd().PhiEngine(n, d, device=DEV)
+    assert eng.phi_gemm == "h2" and eng.ldy == 128 and not eng.sym and eng.Yx3 is not None
+    eng.Yx3 = None
+    eng.step(gpu(X), gpu(S), X_own=gpu(X).clone(), step=0.0, h=None)
+    torch.cuda.synchronize()
+    assert eng.range_guard() is True
+    e = row_err(eng.phi.cpu().numpy(), O.phi(X, S, eng.state.read()[1]))
+    record_parity(float(e.max()))
+    assert e.max() <= ROW_TOL, (e.max(), int(e.argmax()))
+    _, _, eng32 = _phi(X, S, phi_gemm="f32", gram_gemm="h2")
+    assert eng32.phi_gemm == "f32" and eng.splits == 1 and eng32.splits == 1
+    torch.testing.assert_close(eng.dense_D(), eng32.dense_D(), rtol=0, atol=0)
+    assert torch.equal(eng.KY, eng32.KY) and torch.equal(eng.rowsum, eng32.rowsum)
+
+
 @pytest.mark.parametrize("k", [18, 24, 30])
 def test_logreg_scores_row_normalised_with_outlier(k):
     """One particle's w 2^k times the others' (logreg's W image: one FmtH2

@@ -176,6 +176,72 @@ def test_library_exports_kernel_entry_points_and_abi_stays_4():
     assert ctypes.sizeof(_native.Kernel) == 8
 
 
+def _twin_cases(p):
+    """(plain name, _kern name, what the _kern call takes after the shared
+    arguments, failing argument sets without the trailing stream) of the eight
+    operations that exist under two names: null pointers, a wrong ldd where
+    there is one, and a bad sym or size (the sets of the test below and of
+    tests/test_ksd_host.py).  p: a 16-byte aligned address."""
+    mm = [(None, 128, None, 128, 0, 4, 4, None, 1, None, 128, None),
+          (p, 256, p, 128, 0, 4, 4, p, 1, p, 128, p),            # ldd
+          (p, 128, p, 128, 0, 0, 4, p, 1, p, 128, p),            # sizes
+          (p, 128, p, 128, 2, 4, 4, p, 1, p, 128, p)]            # the row block
+    return [
+        ("dsvgd_phi_mm", "dsvgd_phi_mm_kern", "gate order", mm),
+        ("dsvgd_phi_mm_gated", "dsvgd_phi_mm_kern", "order",
+         [a + (None,) for a in mm[:1]] + [a + (p,) for a in mm[1:]]),
+        ("dsvgd_phi_mm_x3", "dsvgd_phi_mm_x3_kern", "order",
+         [(None, 128, None, 128, 0, 4, 4, None, 1, None, 128, None, 0, 0, None),
+          (p, 256, p, 128, 0, 4, 4, p, 1, p, 128, p, 0, 0, None),
+          (p, 128, p, 128, 0, 3, 4, p, 1, p, 128, p, 1, 0, None)]),          # sym, m < n
+        ("dsvgd_phi_mm_h2", "dsvgd_phi_mm_h2_kern", "order",
+         [(None, 128, None, 128, 0, 4, 4, None, 1, None, 128, None, 0, None, None),
+          (p, 256, p, 128, 0, 4, 4, p, 1, p, 128, p, 0, p, None),
+          (p, 128, p, 128, 0, 4, 4, p, 1, p, 128, p, 1, p, None)]),          # sym, ldy % 256
+        ("dsvgd_phi_direct", "dsvgd_phi_direct_kern", "",
+         [(None, 128, None, 128, 0, 4, 4, 1, None, 0.25, 0.0, None, 1, None, 1, None, 1, None, 0),
+          (p, 256, p, 128, 0, 4, 4, 1, p, 0.25, 0.0, None, 1, None, 1, None, 1, None, 0),
+          (p, 128, p, 256, 0, 4, 4, 65, p, 0.25, 0.0, None, 1, None, 1, None, 1, None, 0)]),
+        ("dsvgd_phi_row", "dsvgd_phi_row_kern", "",
+         [(None, 4, None, 4, 4, 3, 0, None, 0.1, None, None),
+          (p, 4, p, 4, 4, 3, 7, p, 0.1, None, None),                         # i >= n
+          (p, 8000, p, 8000, 4, 7950, 0, p, 0.1, None, None)]),              # d > 7936
+        ("dsvgd_phi_row_split", "dsvgd_phi_row_split_kern", "",
+         [(None, 4, None, 4, 4, 3, 0, None, 0.1, None, None, None, 2),
+          (p, 4, p, 4, 4, 3, 0, p, 0.1, None, None, p, 0),                   # blocks
+          (p, 5000, p, 5000, 4, 4100, 0, p, 0.1, None, None, p, 2)]),        # d > 4096
+        ("dsvgd_ksd_rows", "dsvgd_ksd_rows_kern", "",
+         [(None, 128, None, 128, 32, 3, 0, 4, 4, None, 0, 1, None, None),
+          (p, 256, p, 128, 32, 3, 0, 4, 4, p, 0, 1, p, p),
+          (p, 128, p, 128, 32, 3, 1, 3, 4, p, 1, 2, p, p)]),                 # sym, row0 > 0
+        ("dsvgd_ksd_direct", "dsvgd_ksd_direct_kern", "",
+         [(None, 128, 32, 1, 0, 4, 4, None, None, None, None),
+          (p, 256, 128, 3, 2, 4, 4, p, p, p, p),                             # the row block
+          (p, 256, 128, 65, 0, 4, 4, p, p, p, p)]),                          # d > 64
+    ]
+
+
+def test_plain_and_kern_names_are_one_body():
+    """Each operation's plain name and its _kern name with an RBF description
+    refuse the same invalid arguments with the same code and the same text;
+    none of the calls reaches a launch."""
+    from dsvgd import _native as N
+    lib = N.load()
+    rbf = N.Kernel(N.KERNEL_RBF, 0.0)
+    buf = (ctypes.c_double * 64)()
+    p = (ctypes.addressof(buf) + 15) // 16 * 16
+    for plain, kern, extra, cases in _twin_cases(p):
+        for args in cases:
+            got = []
+            tail = (None,) if "gate" in extra else ()
+            tail += (rbf, 0) if "order" in extra else (rbf,)
+            for name, a in ((plain, args), (kern, args + tail)):
+                rc = getattr(lib, name)(*a, None)
+                got.append((rc, lib.dsvgd_last_error()))
+            assert got[0][0] == -1 and got[0][1], (plain, args, got)
+            assert got[0] == got[1], (plain, args, got)
+
+
 def test_kernel_calls_validate_arguments_without_gpu():
     """Every call below fails a check: none reaches a launch."""
     from dsvgd import _native as N
@@ -198,7 +264,7 @@ def test_kernel_calls_validate_arguments_without_gpu():
     rc = lib.dsvgd_phi_mm_x3_kern(None, 128, None, 128, 0, 4, 4, None, 1, None, 128, None, 0, 0,
                                   None, imq, 2, None)
     assert rc == -1 and b"order" in err()
-    # null pointers, in both families (the RBF goes to the call beside it)
+    # null pointers, in both families (one body serves both)
     for kern in (imq, rbf):
         rc = lib.dsvgd_phi_mm_kern(None, 128, None, 128, 0, 4, 4, None, 1, None, 128, None, None,
                                    kern, 0, None)
