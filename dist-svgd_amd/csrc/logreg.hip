@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <string>
 #include <type_traits>
+#include <utility>
 
 #include "gemm_tiles.hpp"
 #include "gemm_x3.hpp"
@@ -301,7 +302,9 @@ __global__ __launch_bounds__(512, 1) void logreg_z_x3p_kernel(
 // sigma'd and split, ARE the A fragments of G . Xd for two 16-deep K-steps
 // when the column image stores each K-step's rows in the order
 // kFusedPerm (position 8h + j <-> row 4h + 8 (j >> 2) + (j & 3)) -- no G
-// in memory, no transpose.  G . Xd of chunk c - 1 runs beside Z of chunk c.
+// in memory, no transpose.  The sweep is software-pipelined three deep: Z of
+// chunk c, sigma of chunk c - 1 (in the gaps between the MFMAs) and G . Xd of
+// chunk c - 2 run in one iteration (see the kernel for the ring order).
 __host__ __device__ constexpr int fused_perm(int p) { return 4 * (p >> 3) + 8 * ((p & 7) >> 2) + (p & 3); }
 
 // Yp[kstep][part][column][16 k]: ysplit_h2_kernel's image with position k of
@@ -329,6 +332,17 @@ __global__ __launch_bounds__(256) void ysplit_h2_perm_kernel(const float* __rest
     *reinterpret_cast<f16x8*>(dst + 8 * sw) = sp[p][0];
     *reinterpret_cast<f16x8*>(dst + 8 * (sw ^ 1)) = sp[p][1];
   }
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop
+// whose index is a constant expression (sched_group_barrier's arguments)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_seq(f, std::make_integer_sequence<int, N>{});
 }
 
 constexpr int kFusedRows = 128;   // particles per block
@@ -369,27 +383,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const float zsc = kLog2e * (*xinv) * rinv[p0 + r];   // z = acc / (t_x s_i)
   // LDS-DMA of chunk c's row image (into abuf[c & 1]) and column image (xbuf[c & 1]):
   // 16-byte units u * 256 + t, wave-uniform LDS bases
-  auto dma_rows = [&](int c) {
+  // (one piece: 4 KiB over the block, 1 KiB per wave-instruction)
+  constexpr int kRowPieces = kFusedXdx / 4096, kColPieces = kFusedXdp / 4096;
+  auto dma_row_piece = [&](int c, int u) {
     char* dst = abuf + (c & 1) * kFusedXdx;
     const int soff = c * kFusedChunk * 32;
-#pragma unroll
-    for (int u = 0; u < kFusedXdx / 4096; ++u) {
-      const int e = u * 256 + t, kp = e >> 6, within = e & 63;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rX, (__attribute__((address_space(3))) void*)(dst + (u * 256 + w * 64) * 16), 16,
-          (int)((int64_t)kp * N_img * 32 + within * 16), soff, 0, 0);
-    }
+    const int e = u * 256 + t, kp = e >> 6, within = e & 63;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(
+        rX, (__attribute__((address_space(3))) void*)(dst + (u * 256 + w * 64) * 16), 16,
+        (int)((int64_t)kp * N_img * 32 + within * 16), soff, 0, 0);
   };
-  auto dma_cols = [&](int c) {
+  auto dma_col_piece = [&](int c, int u) {
     char* dst = xbuf + (c & 1) * kFusedXdp;
     const int soff = c * kFusedXdp;
+    const int e = u * 256 + t;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(
+        rP, (__attribute__((address_space(3))) void*)(dst + (u * 256 + w * 64) * 16), 16,
+        e * 16, soff, 0, 0);
+  };
+  auto dma_rows = [&](int c) {
 #pragma unroll
-    for (int u = 0; u < kFusedXdp / 4096; ++u) {
-      const int e = u * 256 + t;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rP, (__attribute__((address_space(3))) void*)(dst + (u * 256 + w * 64) * 16), 16,
-          e * 16, soff, 0, 0);
-    }
+    for (int u = 0; u < kRowPieces; ++u) dma_row_piece(c, u);
   };
   auto barrier_dma = []() {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -399,7 +413,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int ni = 0; ni < kFusedCols / 32; ++ni)
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[ni][q] = 0.f;
-  V8 g[2][2];   // G of the previous chunk: K-step kk (data rows 16 kk ..), part
+  V8 g[2][2];   // G of an earlier chunk: K-step kk (data rows 16 kk ..), part
   // G . Xd of the chunk whose G is in g, column image in xb
   auto gxd = [&](const char* xb) {
 #pragma unroll
@@ -413,76 +427,197 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         acc[ni] = mfma_fmt<FmtH2>(g[kk][0], bh, acc[ni]);
       }
   };
-  // chunk c: the next chunk's rows and this chunk's columns DMA'd, Z^T of
-  // chunk c (two chains), G . Xd of chunk c - 1 beside it, then sigma(-z)
-  // into the A fragments of chunk c's two K-steps (2^15 G, split).  The
-  // first and last chunks are peeled so that the steady body is one basic
-  // block (the scheduler interleaves the two GEMMs only inside one)
-  auto chunk = [&](int c, auto NEXT_, auto PREV_) {
-    constexpr bool PREV = decltype(PREV_)::value;
-    if constexpr (decltype(NEXT_)::value) dma_rows(c + 1);
-    dma_cols(c);
+  // Iteration c of the sweep is a three-stage pipeline over the chunks:
+  //   Z^T of chunk c        (MFMA, two chains z0 / z1, A from abuf[c & 1]),
+  //   sigma of chunk c - 1  (VALU, in the gaps between the MFMAs),
+  //   G . Xd of chunk c - 2 (MFMA, A = g, B from xbuf[c & 1]),
+  // with the rows of chunk c + 1 and the columns of chunk c - 1 DMA'd beside
+  // them, one piece per half-step.  Z^T leads: its chains are complete four
+  // half-steps before the end, and z = z0 + z1 is read out under the last
+  // four G . Xd half-steps into sv, which the next iteration's sigma takes;
+  // sigma writes a second G set gn, which becomes g at the end of the
+  // iteration.  The order of every sum is the parent's: z0 takes the even
+  // K-steps and z1 the odd ones, acc[ni] the chunks in order (K-step 0, then
+  // 1, of each).
+  //
+  // LDS ring order.  Iteration c has one barrier_dma B(c) (vmcnt(0),
+  // lgkmcnt(0), s_barrier), placed before the MFMAs of its last two
+  // half-steps, after the last ds_read and the last DMA piece it issues:
+  //   buffer       holds    DMA issued in            landed by  read in
+  //   abuf[c & 1]  rows(c)  iteration c-1, < B(c-1)  B(c-1)     after B(c-1) (K-step 0, carried) and
+  //                                                             in iteration c, all reads < B(c)
+  //   xbuf[c & 1]  cols(c)  iteration c+1, < B(c+1)  B(c+1)     iteration c+2, all reads < B(c+2)
+  //   next write:  rows(c+2) in iteration c+1, after B(c); cols(c+2) in iteration c+3, after B(c+2)
+  // so before B(c) the reads go to abuf[c & 1] and xbuf[c & 1] (the columns of
+  // chunk c - 2) and the DMA to abuf[(c+1) & 1] and xbuf[(c-1) & 1]; after
+  // B(c) the only LDS access of iteration c is the read of the next
+  // iteration's first fragments, from a buffer B(c) has just published and
+  // whose next write comes after B(c+1).  No read crosses a barrier: B(c)
+  // waits lgkmcnt(0), and sched_barrier fences keep every ds_read on its side.
+  //
+  // The pipeline's head and tail are peeled (Z only; Z + sigma; ...; sigma +
+  // G . Xd; G . Xd only) so that the steady iteration is one basic block.
+  float sv[16];  // z of the previous chunk, then sigma's intermediate values
+  V8 cf[2];      // the next iteration's first fragments, read after the barrier
+  // NF: what the next iteration starts with (0 nothing carried, 1 a Z^T
+  // half-step, 2 a G . Xd half-step); CARRIED: this one's first is in cf
+  auto chunk = [&](int c, auto NEXT_, auto Z_, auto SIG_, auto GXD_, auto CARRIED_, auto NF_) {
+    constexpr bool NEXT = decltype(NEXT_)::value, Z = decltype(Z_)::value;
+    constexpr bool SIG = decltype(SIG_)::value, GXD = decltype(GXD_)::value;
+    constexpr bool CARRIED = decltype(CARRIED_)::value;
+    constexpr int NF = decltype(NF_)::value;
     const char* ab = abuf + (c & 1) * kFusedXdx;
-    const char* xp = xbuf + ((c - 1) & 1) * kFusedXdp;
-    // step s: Z^T's K-step s (A: the chunk's row image) and, beside it, G .
-    // Xd's (K-step s >> 3, column block s & 7) of chunk c - 1; the LDS
-    // fragments of step s + 1 are read while step s's MFMAs run
-    V8 fa[2][2], fb[2][2];
-    auto rd = [&](int st, int bi) {
-      fa[bi][0] = *reinterpret_cast<const V8*>(ab + (st * 2 + 0) * kFusedChunk * 32 + x3_off(r, h));
-      fa[bi][1] = *reinterpret_cast<const V8*>(ab + (st * 2 + 1) * kFusedChunk * 32 + x3_off(r, h));
-      if constexpr (PREV) {
-        const int kk = st >> 3, ni = st & 7;
-        fb[bi][0] = *reinterpret_cast<const V8*>(xp + (kk * 2 + 0) * kFusedCols * 32 + x3_off(ni * 32 + r, h));
-        fb[bi][1] = *reinterpret_cast<const V8*>(xp + (kk * 2 + 1) * kFusedCols * 32 + x3_off(ni * 32 + r, h));
+    const char* xp = xbuf + (c & 1) * kFusedXdp;
+    const char* nab = abuf + ((c + 1) & 1) * kFusedXdx;
+    const char* nxp = xbuf + ((c + 1) & 1) * kFusedXdp;
+    // half-steps of 3 MFMAs: Z^T's K-step st (A: the chunk's row image) or G
+    // . Xd's (K-step st >> 3, column block st & 7).  With both they alternate
+    // (Z^T first) for 22 half-steps, then Z^T's last kTail, then G . Xd's;
+    // z is read out under the last kRead, a half-step after the chains end
+    constexpr bool BOTH = Z && GXD;
+    constexpr int kTail = 5, kRead = 4;
+    constexpr int NH = (Z ? kFusedKD : 0) + (GXD ? kFusedKD : 0);
+    constexpr int kAlt = 2 * (kFusedKD - kTail);
+    auto is_z = [](int i) constexpr {
+      if (!BOTH) return Z;
+      if (i < kAlt) return (i & 1) == 0;
+      return i < kAlt + kTail;
+    };
+    auto st_of = [](int i) constexpr {
+      if (!BOTH) return i;
+      if (i < kAlt) return i / 2;
+      return kFusedKD - kTail + (i - kAlt) % kTail;
+    };
+    auto rd_z = [&](const char* a, int st, V8* f) {
+      f[0] = *reinterpret_cast<const V8*>(a + (st * 2 + 0) * kFusedChunk * 32 + x3_off(r, h));
+      f[1] = *reinterpret_cast<const V8*>(a + (st * 2 + 1) * kFusedChunk * 32 + x3_off(r, h));
+    };
+    auto rd_g = [&](const char* x, int st, V8* f) {
+      const int kk = st >> 3, ni = st & 7;
+      f[0] = *reinterpret_cast<const V8*>(x + (kk * 2 + 0) * kFusedCols * 32 + x3_off(ni * 32 + r, h));
+      f[1] = *reinterpret_cast<const V8*>(x + (kk * 2 + 1) * kFusedCols * 32 + x3_off(ni * 32 + r, h));
+    };
+    // sigma of the previous chunk (its z is in sv) in slices: pair j (values
+    // 2 j, 2 j + 1) in three stages, one per half-step from kR0 + kP j; with
+    // both GEMMs the last stage ends before the read-out refills sv
+    constexpr int kR0 = BOTH ? 1 : 0, kP = BOTH ? 3 : 1;
+    static_assert(!BOTH || kR0 + kP * 7 + 2 < NH - kRead, "sigma must end before the read-out");
+    V8 gn[2][2];
+    auto stage = [&](int j, int s) {
+#pragma unroll
+      for (int q = 2 * j; q < 2 * j + 2; ++q) {
+        if (s == 0) sv[q] = __builtin_amdgcn_exp2f(sv[q] * zsc);
+        if (s == 1) sv[q] = __builtin_amdgcn_rcpf(1.f + sv[q]) * FmtH2::kAScale;
+        if (s == 2) {
+          const _Float16 hi = (_Float16)sv[q];
+          gn[q >> 3][0][q & 7] = hi;
+          gn[q >> 3][1][q & 7] = (_Float16)(sv[q] - (float)hi);
+        }
       }
     };
     f32x16 z0 = {}, z1 = {};
-    rd(0, 0);
-#pragma unroll
-    for (int st = 0; st < kFusedKD; ++st) {
-      if (st + 1 < kFusedKD) rd(st + 1, (st + 1) & 1);
-      const V8 ah = fa[st & 1][0], al = fa[st & 1][1];
-      f32x16& z = (st & 1) ? z1 : z0;
-      z = mfma_fmt<FmtH2>(al, wf[st][0], z);
-      z = mfma_fmt<FmtH2>(ah, wf[st][1], z);
-      z = mfma_fmt<FmtH2>(ah, wf[st][0], z);
-      if constexpr (PREV) {
-        const int kk = st >> 3, ni = st & 7;
-        const V8 bh = fb[st & 1][0], bl = fb[st & 1][1];
-        acc[ni] = mfma_fmt<FmtH2>(g[kk][1], bh, acc[ni]);   // small terms first
-        acc[ni] = mfma_fmt<FmtH2>(g[kk][0], bl, acc[ni]);
-        acc[ni] = mfma_fmt<FmtH2>(g[kk][0], bh, acc[ni]);
+    V8 fr[2][2];   // a half-step's two LDS fragments, read one half-step ahead
+    if constexpr (CARRIED) {
+      // the carried fragments landed under the previous iteration's last
+      // MFMAs: wait for them here, before this iteration's own reads, so that
+      // every later wait in the block is a counted one
+      __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
+      fr[0][0] = cf[0];
+      fr[0][1] = cf[1];
+    } else {
+      if (is_z(0)) rd_z(ab, st_of(0), fr[0]); else rd_g(xp, st_of(0), fr[0]);
+    }
+    constexpr int kPieces = (NEXT ? kRowPieces : 0) + (SIG ? kColPieces : 0);
+    constexpr int kPer = (kPieces + NH / 2 - 1) / (NH / 2);   // pieces per half-step
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<NH>([&](auto I) {
+      constexpr int i = decltype(I)::value;
+      constexpr int st = st_of(i);
+      constexpr bool isz = is_z(i);
+      if constexpr (i + 1 < NH) {
+        if (is_z(i + 1)) rd_z(ab, st_of(i + 1), fr[(i + 1) & 1]);
+        else rd_g(xp, st_of(i + 1), fr[(i + 1) & 1]);
       }
-    }
-    // order: the first step's reads, then per step the next step's reads
-    // ahead of this step's MFMAs (each read has a step of MFMAs to land)
-    __builtin_amdgcn_sched_group_barrier(0x100, PREV ? 4 : 2, 0);
 #pragma unroll
-    for (int st = 0; st < kFusedKD; ++st) {
-      if (st + 1 < kFusedKD) __builtin_amdgcn_sched_group_barrier(0x100, PREV ? 4 : 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, PREV ? 6 : 3, 0);
-    }
+      for (int u = i * kPer; u < (i + 1) * kPer && u < kPieces; ++u) {
+        if (NEXT && u < kRowPieces) dma_row_piece(c + 1, u);
+        else dma_col_piece(c - 1, u - (NEXT ? kRowPieces : 0));
+      }
+      if constexpr (i == NH - 2) {
+        __builtin_amdgcn_sched_barrier(0);
+        barrier_dma();
+        if constexpr (NF == 1) rd_z(nab, 0, cf);
+        if constexpr (NF == 2) rd_g(nxp, 0, cf);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const V8 fh = fr[i & 1][0], fl = fr[i & 1][1];
+      if constexpr (isz) {
+        f32x16& z = (st & 1) ? z1 : z0;
+        z = mfma_fmt<FmtH2>(fl, wf[st][0], z);
+        z = mfma_fmt<FmtH2>(fh, wf[st][1], z);
+        z = mfma_fmt<FmtH2>(fh, wf[st][0], z);
+      } else {
+        constexpr int kk = st >> 3, ni = st & 7;
+        acc[ni] = mfma_fmt<FmtH2>(g[kk][1], fh, acc[ni]);   // small terms first
+        acc[ni] = mfma_fmt<FmtH2>(g[kk][0], fl, acc[ni]);
+        acc[ni] = mfma_fmt<FmtH2>(g[kk][0], fh, acc[ni]);
+      }
+      if constexpr (SIG) {
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float zz = (z0[q] + z1[q]) * zsc;
-      const float gv = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(zz)) * FmtH2::kAScale;
-      const _Float16 hi = (_Float16)gv;
-      g[q >> 3][0][q & 7] = hi;
-      g[q >> 3][1][q & 7] = (_Float16)(gv - (float)hi);
+        for (int s = 0; s < 3; ++s)
+          if (i - s >= kR0 && (i - s - kR0) % kP == 0 && (i - s - kR0) / kP < 8)
+            stage((i - s - kR0) / kP, s);
+      }
+      if constexpr (BOTH && i >= NH - kRead) {   // the read-out, 4 values per half-step
+        // (an empty statement that redefines z0 / z1 where they are: the
+        // copies out of the accumulators then sit in this half-step, not
+        // right behind the chains' last MFMAs, where each waits 12 states)
+        asm volatile("" : "+a"(z0), "+a"(z1));
+#pragma unroll
+        for (int q = (i - (NH - kRead)) * (16 / kRead); q < (i + 1 - (NH - kRead)) * (16 / kRead); ++q)
+          sv[q] = z0[q] + z1[q];
+      }
+      // inside the half-step: its reads and DMA piece first, then the vector
+      // instructions after each MFMA
+      if constexpr (i != NH - 2) {
+        if constexpr (i + 1 < NH) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        if constexpr (i * kPer < kPieces) __builtin_amdgcn_sched_group_barrier(0x020, kPer, 0);
+      }
+      constexpr int fill = BOTH ? (i >= NH - kRead ? 4 : (SIG ? 2 : 0)) : (SIG ? 6 : 0);
+#pragma unroll
+      for (int m = 0; m < 3; ++m) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        if constexpr (fill > 0) __builtin_amdgcn_sched_group_barrier(0x402, fill, 0);
+      }
+      // a fence after every half-step keeps the MFMAs in this order
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    if constexpr (Z && !BOTH) {   // (head of the pipeline: nothing to hide it under)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) sv[q] = z0[q] + z1[q];
     }
-    barrier_dma();
+    if constexpr (SIG) {
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) g[kk][p] = gn[kk][p];
+    }
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-  // data slice blockIdx.y: chunks [c0, c0 + cpb) (>= 2, checked by the host)
+  constexpr std::integral_constant<int, 0> nf_none{};
+  constexpr std::integral_constant<int, 1> nf_z{};
+  constexpr std::integral_constant<int, 2> nf_g{};
+  // data slice blockIdx.y: chunks [c0, c0 + cpb) (>= 3, checked by the host)
   const int c0 = (int)blockIdx.y * cpb, c1 = min(nchunks, c0 + cpb);
   GW += (int64_t)blockIdx.y * n * ldg;
   dma_rows(c0);
   barrier_dma();
-  chunk(c0, yes, no);
-  for (int c = c0 + 1; c + 1 < c1; ++c) chunk(c, yes, yes);
-  chunk(c1 - 1, no, yes);
+  chunk(c0, yes, yes, no, no, no, nf_z);             // Z(c0)
+  chunk(c0 + 1, yes, yes, yes, no, yes, nf_z);       // Z(c0 + 1), sigma(c0)
+  for (int c = c0 + 2; c + 1 < c1; ++c) chunk(c, yes, yes, yes, yes, yes, nf_z);
+  chunk(c1 - 1, no, yes, yes, yes, yes, nf_g);       // the last Z: no rows to fetch
+  chunk(c1, no, no, yes, yes, yes, nf_none);         // sigma(c1 - 1), G . Xd(c1 - 2)
   gxd(xbuf + ((c1 - 1) & 1) * kFusedXdp);
   // GW[i][c] = acc 2^-15 / s_c
 #pragma unroll
@@ -825,8 +960,9 @@ static int logreg_step(const float* X, int64_t ldx, int64_t n, int64_t p, float 
         w.N_pad % kFusedChunk == 0 && w.N_pad >= 2 * kFusedChunk && w.n_pad % kFusedRows == 0) {
       const int z = fused_splits(w.n_pad, w.N_pad);
       const int nchunks = (int)(w.N_pad / kFusedChunk);
-      // every slice takes nchunks / z >= 2 whole chunks (none dropped)
-      DSVGD_REQUIRE(nchunks % z == 0 && nchunks / z >= 2, "fused score: unequal data slices");
+      // every slice takes nchunks / z >= 3 whole chunks (none dropped; the
+      // kernel's peeled head and tail are 3 chunks deep)
+      DSVGD_REQUIRE(nchunks % z == 0 && nchunks / z >= 3, "fused score: unequal data slices");
       hipLaunchKernelGGL(logreg_fused_kernel, dim3((unsigned)(w.n_pad / kFusedRows), (unsigned)z),
                          dim3(256), 0, s, (const _Float16*)Wx, w.n_pad,
                          (const _Float16*)(base + w.off_xdx), w.N_pad,
