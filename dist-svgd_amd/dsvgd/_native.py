@@ -180,6 +180,17 @@ SIGNATURES = {
     "dsvgd_score_gmix": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _f, _p, _i64,
                                 _p]),
     "dsvgd_gmix_assign": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p]),
+    # the softmax-regression target (csrc/softmax.hip)
+    "dsvgd_score_softmax": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _f, _f,
+                                   _f, _p, _i64, _p]),
+    "dsvgd_score_softmax_window": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _f,
+                                          _f, _f, _p, _i64, _p, _i64, _p]),
+    "dsvgd_score_softmax_rows": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _f,
+                                        _f, _f, _p, _i64, _p, _i64, _p]),
+    "dsvgd_softmax_small_rows": (_i64, []),
+    "dsvgd_softmax_predict_workspace_bytes": (_c.c_size_t, [_i64, _i64, _i64]),
+    "dsvgd_softmax_predict": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64,
+                                     _p, _p]),
     # the AdaGrad-conditioned update (csrc/adagrad.hip)
     "dsvgd_adagrad_step": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _f, _f, _f, _p]),
     # the wide blocked Gauss-Seidel sweep (ABI 4)

@@ -23,6 +23,11 @@ the two reductions over them in fp64 torch on the device.
 dsvgd.targets.GaussianMixture: every particle's log density and its most
 responsible component in `dsvgd_gmix_assign` (csrc/gmix.hip), the shares by a
 bincount on the device.
+
+`softmax_predict`, `softmax_accuracy` and `softmax_loglik` evaluate the
+particles of dsvgd.targets.SoftmaxRegression on a test set: the mixture's
+class probabilities in `dsvgd_softmax_predict` (csrc/softmax.hip), the two
+reductions over them in torch on the device (the log-likelihood in fp64).
 """
 import math
 
@@ -227,6 +232,45 @@ def mode_shares(particles, target):
     comp = _gmix_assign(particles, target)[1]
     counts = torch.bincount(comp.long(), minlength=target.K)
     return counts.double() / comp.numel()
+
+
+def softmax_predict(particles, target_or_classes, x_test):
+    """(Nt, C) device tensor P[q][c] = (1/n) sum_i softmax_c(W_i x_test_q): the
+    posterior-predictive class probabilities of the particle mixture
+    (dsvgd.targets.SoftmaxRegression's layout), through `dsvgd_softmax_predict`
+    (the sum over the particles in a fixed order: the same bits on every
+    call).  target_or_classes: the SoftmaxRegression target, or its C."""
+    C = int(getattr(target_or_classes, "classes", target_or_classes))
+    X = torch.as_tensor(particles)
+    dev = N.require_gpu(X.device if X.is_cuda else "cuda")
+    X = _device_f32(X, dev)
+    n, d = X.shape
+    xt = _device_f32(x_test, dev)
+    if xt.dim() != 2 or d != 1 + C * xt.shape[1]:
+        raise ValueError("x_test must be (Nt, p) with d = 1 + C p = %d" % d)
+    Nt, p = xt.shape
+    nbytes = N.load().dsvgd_softmax_predict_workspace_bytes(n, Nt, C)
+    ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device=dev)
+    P = torch.empty(Nt, C, dtype=torch.float32, device=dev)
+    N.call("dsvgd_softmax_predict", N.ptr(X), N.ld(X), n, d, N.ptr(xt), N.ld(xt), Nt, C, p,
+           N.ptr(P), N.ld(P), N.ptr(ws), N.stream(dev))
+    return P
+
+
+def softmax_accuracy(particles, target, x_test, y_test):
+    """Fraction of the test rows whose most probable class under
+    softmax_predict is y_test (a Python float)."""
+    P = softmax_predict(particles, target, x_test)
+    y = torch.as_tensor(y_test).reshape(-1).to(device=P.device, dtype=torch.int64)
+    return int((P.argmax(1) == y).sum()) / P.shape[0]
+
+
+def softmax_loglik(particles, target, x_test, y_test):
+    """Mean test log-likelihood of the particle mixture, mean_q log P[q, y_q],
+    reduced in fp64 on the device (a Python float)."""
+    P = softmax_predict(particles, target, x_test).double()
+    y = torch.as_tensor(y_test).reshape(-1).to(device=P.device, dtype=torch.int64)
+    return float(torch.log(torch.gather(P, 1, y[:, None])[:, 0]).mean())
 
 
 def predictive_prob(particles, x_test):

@@ -10,7 +10,9 @@ particles in one batched device call:
   :class:`LogisticRegression` (experiments/logreg.py:45-58, two MFMA GEMMs),
   :class:`BayesianNN` (beyond the reference: one kernel, csrc/bnn.hip),
   :class:`GaussianMixture` (K components with diagonal precisions in d
-  dimensions: one kernel, csrc/gmix.hip);
+  dimensions: one kernel, csrc/gmix.hip),
+  :class:`SoftmaxRegression` (multiclass logistic regression: two f32 MFMA
+  products around a lane-local softmax, csrc/softmax.hip);
 * any other `logp` callable is wrapped by :class:`CallableTarget`, which runs
   the user's own torch code under ``torch.func.vmap(torch.func.grad(logp))``
   on the particles' device (user code, not a dsvgd compute path).
@@ -533,6 +535,137 @@ class GaussianMixture(BuiltinTarget):
         N.call("dsvgd_gmix_assign", N.ptr(X), N.ld(X), n, d, N.ptr(mu), N.ld(mu), N.ptr(lam),
                N.ld(lam), N.ptr(c), self.K, N.ptr(logp), N.ptr(comp), N.stream(X.device))
         return logp, comp
+
+
+class SoftmaxRegression(_Windowed, BuiltinTarget):
+    """Bayesian softmax (multiclass logistic) regression: data rows xd_q in R^p
+    with labels y_q in {0..C-1}, no bias term (append a ones column, as for
+    LogisticRegression).  Not in the reference, whose users would pass this logp.
+
+        x = [log alpha | vec(W)] with W (C, p) row-major,   d = 1 + C p
+        W_ck ~ N(0, 1 / alpha),  alpha ~ Gamma(a0, b0)
+        log p = sum_q log softmax(W xd_q)[y_q] + (C p / 2) x_0 - alpha |W|^2 / 2
+                + a0 x_0 - b0 alpha
+
+    alpha is carried as its log WITH the log-Jacobian (the a0 x_0 term): this
+    is BayesianNN's convention, not LogisticRegression's, which follows the
+    reference's logreg and has none.
+
+    classes=None takes C = max(y) + 1.  2 <= C <= MAX_CLASSES, p >= 1 and
+    d <= MAX_D.  The score is csrc/softmax.hip: both products on the f32 MFMA
+    for more than a few particles, a workgroup per particle below that (the
+    sequential order's per-row refresh).
+
+    batch=B with 1 <= B < N scores a minibatch, by BayesianNN's rules: the
+    data sum over the cyclic window of B rows that starts at a cursor kept on
+    the device, weighted N / B, the prior terms once.  next_batch() moves the
+    window by B rows, reset_batch(t) puts it at (t B) mod N; `logp` stays the
+    full-data density and `full` is the full-data twin (evaluation,
+    dsvgd.metrics.ksd).  batch=None or batch >= N is the full-data target."""
+
+    MAX_CLASSES = 16    # DSVGD_SOFTMAX_MAX_CLASSES
+    MAX_D = 1024        # dsvgd_score_softmax
+
+    def __init__(self, x_train, y_train, classes=None, a0=1.0, b0=1.0, batch=None):
+        self.x = torch.as_tensor(x_train).detach().to(torch.float32)
+        y = torch.as_tensor(y_train).detach().reshape(-1)
+        if self.x.dim() != 2 or self.x.shape[0] != y.shape[0] or self.x.shape[0] < 1 \
+                or self.x.shape[1] < 1:
+            raise ValueError("x_train must be (N, p) and y_train (N,), N, p >= 1")
+        if y.dtype == torch.bool:
+            raise ValueError("labels must be integers in [0, classes)")
+        if y.is_floating_point():
+            if not bool((torch.isfinite(y) & (y == torch.floor(y))).all()):
+                raise ValueError("labels must be integers in [0, classes)")
+        elif y.is_complex():
+            raise ValueError("labels must be integers in [0, classes)")
+        y = y.to(device="cpu", dtype=torch.int64)
+        if classes is None:
+            classes = int(y.max()) + 1
+        if isinstance(classes, bool) or int(classes) != classes:
+            raise ValueError("classes must be an integer, got %r" % (classes,))
+        self.classes = int(classes)
+        if not 2 <= self.classes <= self.MAX_CLASSES:
+            raise ValueError("classes must be in [2, %d], got %d" % (self.MAX_CLASSES, self.classes))
+        if int(y.min()) < 0 or int(y.max()) >= self.classes:
+            raise ValueError("labels must lie in [0, %d)" % self.classes)
+        if self.d > self.MAX_D:
+            raise ValueError("SoftmaxRegression supports d = 1 + C p <= %d, got %d"
+                             % (self.MAX_D, self.d))
+        self.y = y.to(torch.int32)
+        self.a0, self.b0 = float(a0), float(b0)
+        self._init_batch(batch)
+        self._dev = {}
+
+    @property
+    def N(self):
+        return self.x.shape[0]
+
+    @property
+    def p(self):
+        return self.x.shape[1]
+
+    @property
+    def C(self):
+        return self.classes
+
+    @property
+    def d(self):
+        return 1 + self.classes * self.x.shape[1]
+
+    def unpack(self, x):
+        """(log alpha, W (C, p)) views of a particle."""
+        return x[0], x[1:].reshape(self.classes, self.p)
+
+    def logp(self, x):
+        if x.shape[-1] != self.d:
+            raise ValueError("SoftmaxRegression target has d = 1 + C p = %d" % self.d)
+        xd = self.x.to(device=x.device, dtype=x.dtype)
+        y = self.y.to(device=x.device, dtype=torch.int64)
+        la, W = self.unpack(x)
+        z = xd @ W.T
+        lik = (torch.gather(z, 1, y[:, None])[:, 0] - torch.logsumexp(z, 1)).sum()
+        alpha = torch.exp(la)
+        return (lik + 0.5 * (self.d - 1) * la - 0.5 * alpha * (W * W).sum()
+                + self.a0 * la - self.b0 * alpha)
+
+    def _params(self, dev):
+        if dev not in self._dev:
+            self._dev[dev] = (self.x.to(dev).contiguous(), self.y.to(dev).contiguous())
+        return self._dev[dev]
+
+    def fingerprint(self):
+        """Digest of the data and the model (C, a0, b0, and the batch of a
+        minibatch target)."""
+        import hashlib
+        import struct
+        h = hashlib.sha1(b"softmax")
+        h.update(struct.pack("<qqqdd", self.N, self.p, self.classes, self.a0, self.b0))
+        if self.batch is not None:
+            h.update(struct.pack("<q", self.batch))
+        h.update(_host_bytes(self.x))
+        h.update(_host_bytes(self.y))
+        return h.hexdigest()
+
+    def score(self, X, out, scale=1.0, form=None):
+        """out = scale * grad log p(X).  form="rows" takes the
+        workgroup-per-particle kernel whatever n is (scripts/softmax_timing.py)."""
+        n, d = X.shape
+        assert d == self.d, "SoftmaxRegression target has d = 1 + C p = %d" % self.d
+        if form not in (None, "rows"):
+            raise ValueError("form must be None or 'rows'")
+        xd, y = self._params(X.device)
+        head = (N.ptr(X), N.ld(X), n, d, N.ptr(xd), N.ld(xd), N.ptr(y), self.N, self.classes,
+                self.p, self.a0, self.b0, float(scale))
+        tail = (N.ptr(out), N.ld(out), N.stream(X.device))
+        if self.batch is not None:
+            cur = N.ptr(self._window(X.device))
+            N.call("dsvgd_score_softmax_rows" if form else "dsvgd_score_softmax_window",
+                   *head, cur, self.batch, *tail)
+        elif form:
+            N.call("dsvgd_score_softmax_rows", *head, None, self.N, *tail)
+        else:
+            N.call("dsvgd_score_softmax", *head, *tail)
 
 
 class CallableTarget(Target):

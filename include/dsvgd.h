@@ -967,6 +967,68 @@ int dsvgd_gmix_assign(const float* X, int64_t ldx, int64_t n, int64_t d, const f
                       int64_t ldm, const float* lam, int64_t ldl, const float* c, int64_t K,
                       float* logp_out, int32_t* comp_out, void* stream);
 
+/* ---- Bayesian softmax (multiclass logistic) regression (csrc/softmax.hip) --
+ * Data rows xd_q in R^p (N x p, ldxd >= p) with labels y_q in {0..C-1} (int32);
+ * no bias term: the caller appends a ones column, as for the logistic
+ * regression.  A particle is x = [log a | vec(W)], W of shape C x p row-major,
+ * d = 1 + C p.  Priors W_ck ~ N(0, 1/a) and a ~ Gamma(a0, b0), a carried as its
+ * log with the log-Jacobian (dsvgd_score_bnn's convention, not
+ * dsvgd_score_logreg's, which has none):
+ *   z_qc  = w_c . xd_q,  pi_qc = softmax_c(z_q.),  a = exp(x_0),
+ *   log p = sum_q [z_{q,y_q} - logsumexp_c z_qc] + (C p / 2) x_0 - (a/2) |W|^2
+ *           + a0 x_0 - b0 a,
+ *   d/dW_c = sum_q (1[y_q = c] - pi_qc) xd_q - a W_c,
+ *   d/dx_0 = C p / 2 - (a/2) |W|^2 + a0 - b0 a.
+ * S = scale * grad log p for n particles, in exact fp32 (no input is split or
+ * scaled), the softmax with its maximum subtracted before any exponent.
+ * n > 16: v_mfma_f32_32x32x2_f32 for both products, a workgroup of four waves
+ * per 32 particles, the waves sharing the data rows in chunks of 32 through
+ * LDS, the softmax lane-local in two passes over the classes, G in registers;
+ * more than 16 output tiles (a class x 32 columns each) split over workgroups.
+ * n <= 16 (the sequential order's one-particle refresh): a workgroup per
+ * particle on the VALU.  The two forms need not agree bit for bit; within a
+ * form every sum runs in a fixed order without atomics (the same bits on every
+ * call) and a particle's score depends neither on its row nor on the other
+ * particles.  No workspace, no allocation, no host sync: only enqueues work.
+ * 2 <= C <= DSVGD_SOFTMAX_MAX_CLASSES, p >= 1, d = 1 + C p <= 1024, any n >= 1,
+ * 1 <= N <= 2^30; ldx, lds >= d; S's pad columns are left alone.  Absent in
+ * the reference: replaces a user logp of this model differentiated by autograd
+ * (dsvgd/sampler.py:28-33 _dlogp). */
+#define DSVGD_SOFTMAX_MAX_CLASSES 16
+int dsvgd_score_softmax(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Xd,
+                        int64_t ldxd, const int32_t* y, int64_t N, int64_t C, int64_t p, float a0,
+                        float b0, float scale, float* S, int64_t lds, void* stream);
+/* The minibatch estimate of the same score: the data sum over the cyclic
+ * window of B rows that starts at row c = *cursor, rows (c + q) mod N for
+ * q < B, weighted N / B, and the prior terms once; scale applies to the sum.
+ * cursor: one int64 in device memory, read by every workgroup (any value:
+ * taken mod N) -- the window rule of dsvgd_score_bnn_window;
+ * dsvgd_window_advance moves it.  1 <= B <= N.  The same kernels as
+ * dsvgd_score_softmax, which is the window of all N rows from row 0. */
+int dsvgd_score_softmax_window(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Xd,
+                               int64_t ldxd, const int32_t* y, int64_t N, int64_t C, int64_t p,
+                               float a0, float b0, float scale, const int64_t* cursor, int64_t B,
+                               float* S, int64_t lds, void* stream);
+/* The same with the one-workgroup-per-particle form for every n (cursor may
+ * be NULL: the window starts at row 0): what the tile form is timed against
+ * (scripts/softmax_timing.py).  dsvgd_softmax_small_rows: the largest n the
+ * two entry points above give to that form. */
+int dsvgd_score_softmax_rows(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Xd,
+                             int64_t ldxd, const int32_t* y, int64_t N, int64_t C, int64_t p,
+                             float a0, float b0, float scale, const int64_t* cursor, int64_t B,
+                             float* S, int64_t lds, void* stream);
+int64_t dsvgd_softmax_small_rows(void);
+/* Posterior-predictive class probabilities of a test set:
+ *   P[q][c] = (1/n) sum_i softmax_c(W_i xt_q),  W_i = X[i][1:d] (alpha unused),
+ * P: Nt x C (ldp >= C), Xt: Nt x p (ldxt >= p).  fp32; the sum over the
+ * particles in a fixed order (per-workgroup partial sums in the workspace,
+ * then a finish kernel): the same bits on every call.  workspace of
+ * dsvgd_softmax_predict_workspace_bytes(n, Nt, C) bytes. */
+size_t dsvgd_softmax_predict_workspace_bytes(int64_t n, int64_t Nt, int64_t C);
+int dsvgd_softmax_predict(const float* X, int64_t ldx, int64_t n, int64_t d, const float* Xt,
+                          int64_t ldxt, int64_t Nt, int64_t C, int64_t p, float* P, int64_t ldp,
+                          void* workspace, void* stream);
+
 /* ---- AdaGrad-conditioned update of the Jacobi order (csrc/adagrad.hip) ----
  * Liu & Wang's rule, per entry of the m moved rows; p = phi (m x d, ldphi) is
  * the whole direction, the h * W2 rows included:
