@@ -15,6 +15,7 @@
 #include "gemm_tiles.hpp"
 #include "gemm_x3.hpp"
 #include "gram_rs.hpp"
+#include "gram_sr.hpp"
 #include "gram_w1.hpp"
 #include "select.hpp"
 
@@ -461,23 +462,40 @@ __global__ __launch_bounds__(512, 1) void sqdist_x3w_kernel(
 }
 
 // The one-kernel Gram units (128 x 256, four candidate slots each) run on
-// gram_rs_kernel (split roles: MFMA waves + epilogue waves, gram_rs.hpp;
-// default) or gram_w1_kernel (one wave per SIMD, the epilogue between the
-// MFMAs); the same arguments, units, slots and D bits.  dsvgd_gram_set_rs.
-static int g_gram_rs = 1;
+// gram_sr_kernel (the strip's image resident in LDS, gram_sr.hpp; default
+// where it applies: the panel-layout D of dsvgd_sqdist_h2 at 16 K-steps),
+// gram_rs_kernel (split roles: MFMA waves + epilogue waves, gram_rs.hpp) or
+// gram_w1_kernel (one wave per SIMD, the epilogue between the MFMAs); the
+// same units, slots and D bits.  dsvgd_gram_set_rs.
+static int g_gram_rs = 2;
 // strips per unit group of the split-role Gram's walk (GramUnitWalk G: the
 // strips whose image an XCD's L2 keeps while the column pairs stream past;
 // B is fetched once per group).  8 or 16, dsvgd_gram_set_group.
 static int g_gram_group = 8;
 static void* g_gram_stamps = nullptr;  // dsvgd_gram_debug_stamps (probe 8)
+static int g_gram_last = -1;           // dsvgd_gram_last_kernel
 static int gram_group() { return g_gram_rs ? g_gram_group : GramW1::kGroup; }
 
 template <int SM, bool SY>
 int launch_gram_units(const _Float16* Yg, int64_t img, const float* norms, const float* rsc,
                       int64_t row0, int64_t m, int64_t n, int64_t n_pad, int nk, float* D,
                       dsvgd_select_state* st, float* cand, int64_t tot, int Tm, int Tc, int jp_off,
-                      int64_t base, int64_t ns_total, int w2all, const float* gate, hipStream_t s) {
+                      int64_t base, int64_t ns_total, int w2all, const float* gate, hipStream_t s,
+                      bool sr_ok = false) {
   int bw = 0, rc = 0;
+  if (g_gram_rs >= 2 && g_gram_rs <= 4 && sr_ok && nk == GramSR::kSteps && !w2all && !gate) {
+    // 2: the stagger and the MFMA phase's priority; 3: no stagger; 4: no priority
+    const int flags = g_gram_rs == 2 ? GramSR::kStagger | GramSR::kPrio
+                                     : (g_gram_rs == 3 ? GramSR::kPrio : GramSR::kStagger);
+    if ((rc = persistent_blocks(reinterpret_cast<const void*>(&gram_sr_kernel<SM, SY>), &bw,
+                                GramSR::kThreads)))
+      return rc;
+    hipLaunchKernelGGL((gram_sr_kernel<SM, SY>), dim3((unsigned)bw), dim3(GramSR::kThreads), 0, s,
+                       Yg, img, norms, rsc, row0, m, n, n_pad, D, st, cand, Tm, Tc, jp_off,
+                       gram_group(), base, ns_total, flags);
+    g_gram_last = 2;
+    return check_launch("gram_sr");
+  }
   if (g_gram_rs) {
     // the A/B probe variants (gram_rs.hpp VAR) exist for the headline's form only
     auto launch = [&](auto VAR_) {
@@ -493,6 +511,7 @@ int launch_gram_units(const _Float16* Yg, int64_t img, const float* norms, const
         hipLaunchKernelGGL((gram_rs_kernel<SM, SY, 0, VAR, KG>), dim3((unsigned)bw),
                            dim3(GramRS::kThreads), 0, s, Yg, img, norms, rsc, row0, m, n, n_pad,
                            nk, D, st, cand, tot, Tm, Tc, jp_off, base, ns_total, w2all, gate, wo);
+        g_gram_last = 1;
         return check_launch("gram_rs");
       };
       // (the caller's unit count came from the same group: gram_group())
@@ -515,6 +534,7 @@ int launch_gram_units(const _Float16* Yg, int64_t img, const float* norms, const
   hipLaunchKernelGGL((gram_w1_kernel<SM, SY>), dim3((unsigned)bw), dim3(GramW1::kThreads), 0, s, Yg,
                      img, norms, rsc, row0, m, n, n_pad, nk, D, st, cand, tot, Tm, Tc, jp_off, base,
                      ns_total, w2all, gate);
+  g_gram_last = 0;
   return check_launch("gram_w1");
 }
 
@@ -582,6 +602,7 @@ int launch_sqdist_x3(const typename F::E* Yg, const float* norms, int64_t row0, 
   const int64_t dp = roundup(d, 32), m_pad = roundup(m, 128), n_pad = roundup(n, 128);
   const int64_t img = gram_img_rows(n);
   const bool sym = m == n && row0 == 0;
+  g_gram_last = -1;  // no part of this call on the one-kernel Gram units so far
   constexpr int KS = F::P == 2 ? kGramKS : 1;
   const int nk = (int)(dp / kX3Step / KS);  // ring stages per tile (dp is a multiple of 32)
   int rc = 0;
@@ -635,10 +656,11 @@ int launch_sqdist_x3(const typename F::E* Yg, const float* norms, int64_t row0, 
       if constexpr (F::P == 2) {
         rc = P.sym ? launch_gram_units<SM, true>((const _Float16*)Yg, img, norms, rsc, row0, m, n,
                                                  n_pad, nk * KS, D, st, cand, tot, wk.Tm, wk.Tc,
-                                                 P.bj_off, base, ns_total, 0, nullptr, s)
+                                                 P.bj_off, base, ns_total, 0, nullptr, s, true)
                    : launch_gram_units<SM, false>((const _Float16*)Yg, img, norms, rsc, row0, m,
                                                   n, n_pad, nk * KS, D, st, cand, tot, wk.Tm,
-                                                  wk.Tc, P.bj_off, base, ns_total, 0, nullptr, s);
+                                                  wk.Tc, P.bj_off, base, ns_total, 0, nullptr, s,
+                                                  true);
         if (rc) return rc;
       }
       base += tot * GramW1::kSlots;
@@ -1034,6 +1056,8 @@ int dsvgd_gram_set_group(int g) {
   g_gram_group = g == 16 ? 16 : 8;
   return prev;
 }
+
+int dsvgd_gram_last_kernel(void) { return g_gram_last; }
 
 int dsvgd_gram_set_rs(int on) {
   const int prev = g_gram_rs;

@@ -79,6 +79,7 @@ SIGNATURES = {
     "dsvgd_phi_set_symrow": (_int, [_int]),
     "dsvgd_phi_set_finish_vec": (_int, [_int]),
     "dsvgd_gram_set_rs": (_int, [_int]),
+    "dsvgd_gram_last_kernel": (_int, []),
     "dsvgd_gram_set_group": (_int, [_int]),
     "dsvgd_set_cu_reserve": (_int, [_int]),
     "dsvgd_gram_debug_stamps": (_int, [_p]),

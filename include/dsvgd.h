@@ -239,7 +239,15 @@ int64_t dsvgd_phi_splits(int64_t m, int64_t n, int64_t ldy);
  * 0 = two launches split at each row block's diagonal tile (DS 1 + DS 2). */
 int dsvgd_phi_set_symrow(int on);
 /* The one-kernel FmtH2 Gram units (dsvgd_sqdist_h2, dsvgd_sqdist_h2_parts):
- * 1 (default) = gram_rs_kernel, split roles -- four waves issue only the
+ * 2 (default) = gram_sr_kernel where it applies -- the panel-layout D of
+ * dsvgd_sqdist_h2 at a padded depth of 256 (16 K-steps), none / bracket
+ * select: a block keeps its 128-row strip's whole image in LDS, every wave
+ * computes 128 x 64 tiles and writes them out from its own accumulators, the
+ * second wave of each SIMD starting half a tile late; gram_rs_kernel
+ * everywhere else (deeper images, dsvgd_sqdist_h2_parts, dsvgd_w2_cost_h2).
+ * 3, 4: the same without the stagger / without priority 1 in the MFMA phase
+ * (A/B).
+ * 1 = gram_rs_kernel, split roles -- four waves issue only the
  * MFMAs (and stage the strip image by LDS-DMA), four waves write the
  * previous tile's epilogue (D values, bracket accounting, stores) from an
  * LDS hand-off; 0 = gram_w1_kernel, one wave per SIMD with the epilogue
@@ -249,6 +257,12 @@ int dsvgd_phi_set_symrow(int on);
  * given to dsvgd_gram_debug_stamps; 9: the MFMA waves' B ring 4 deep).
  * Returns the previous setting. */
 int dsvgd_gram_set_rs(int on);
+/* The kernel the last launch of one-kernel Gram units ran on: 0
+ * gram_w1_kernel, 1 gram_rs_kernel, 2 gram_sr_kernel.  dsvgd_sqdist_h2 and
+ * dsvgd_sqdist_x3 reset it to -1 on entry, so -1 after one of them means the
+ * call had no such units (roundup(d, 32) not a multiple of 256, the histogram
+ * select: the 8-wave kernel).  For tests of the dispatch above. */
+int dsvgd_gram_last_kernel(void);
 /* CUs the persistent launches issued after this call leave free (returns
  * the previous; 0 = none): the pipelined Gauss-Seidel sweep sets it around
  * its side-stream passes so the walk (one workgroup, most of a CU's LDS)
