@@ -11,6 +11,7 @@ from . import kernels, metrics, targets  # noqa: E402
 from .kernels import IMQ, RBF  # noqa: E402
 from .adagrad import AdaGrad  # noqa: E402
 from .engine import PhiEngine  # noqa: E402
+from .projection import Projection  # noqa: E402
 
-__all__ = ["name", "Sampler", "DistSampler", "RBF", "IMQ", "AdaGrad", "PhiEngine", "kernels", "metrics",
-           "targets"]
+__all__ = ["name", "Sampler", "DistSampler", "RBF", "IMQ", "AdaGrad", "PhiEngine", "Projection",
+           "kernels", "metrics", "targets"]

@@ -259,6 +259,13 @@ SIGNATURES = {
     "dsvgd_mmd_workspace_doubles": (_c.c_size_t, [_i64]),
     "dsvgd_mmd_rows": (_int, [_p, _i64, _i64, _i64, _p, _k, _int, _i64, _i64, _p, _p]),
     "dsvgd_mmd_finish": (_int, [_p, _i64, _i64, _int, _i64, _i64, _p, _p, _p, _p, _p, _p]),
+    # the dense products of projected SVGD (csrc/project.hip)
+    "dsvgd_proj_gram_slices": (_i64, [_i64, _i64]),
+    "dsvgd_proj_gram_workspace_bytes": (_c.c_size_t, [_i64, _i64]),
+    "dsvgd_proj_gram": (_int, [_p, _i64, _p, _i64, _i64, _i64, _int, _p, _p, _i64, _p]),
+    "dsvgd_proj_apply": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _p,
+                                _i64, _p]),
+    "dsvgd_proj_lift": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _f, _p, _i64, _p, _i64, _p]),
 }
 
 

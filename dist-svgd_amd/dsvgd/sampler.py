@@ -18,7 +18,9 @@ Extensions (keyword-only, defaults keep the reference behaviour):
   ksd_every           record the kernelized Stein discrepancy every k-th
                       timestep into `sampler.diagnostics` (default off);
   adagrad             None (fixed steps), True or a dsvgd.AdaGrad: Liu &
-                      Wang's AdaGrad-conditioned steps (order="jacobi").
+                      Wang's AdaGrad-conditioned steps (order="jacobi");
+  project             None or a dsvgd.Projection: projected SVGD, the particles
+                      interact in an r-dimensional subspace (order="jacobi").
 A target with minibatches (targets.BayesianNN(batch=...) or
 targets.LogisticRegression(batch=...)) is scored on window t of its data at
 iteration t, in both orders.
@@ -35,6 +37,7 @@ from . import _native as N
 from .adagrad import resolve_adagrad
 from .engine import AdaGradState, PhiEngine, SelectState, StepGraph, sequential_sweep
 from .kernels import resolve_kernel
+from .projection import Projection
 from .targets import BuiltinTarget, resolve_target
 
 
@@ -55,7 +58,7 @@ class Sampler(object):
         self.diagnostics = None   # sample(ksd_every=k) leaves its KSD records here
 
     def sample(self, n, num_iter, step_size, *, order="sequential", device=None, verbose=True,
-               graphs=True, ksd_every=None, adagrad=None):
+               graphs=True, ksd_every=None, adagrad=None, project=None):
         """Generate samples using SVGD (sampler.py:42-74).
 
         adagrad=True or a dsvgd.AdaGrad moves the particles by the AdaGrad
@@ -67,7 +70,18 @@ class Sampler(object):
         at timesteps 0, k, 2k, .. <= num_iter, with the bandwidth the sampler
         used there, into `self.diagnostics` (a DataFrame: timestep, ksd,
         ksd2_v, ksd2_u, h; ksd = sqrt(max(ksd2_v, 0))), read back once after
-        the loop.  The returned particles do not change by a bit."""
+        the loop.  The returned particles do not change by a bit.
+
+        project=dsvgd.Projection(rank=r) or (basis=Psi): projected SVGD
+        (dsvgd.projection; order="jacobi", fixed steps).  The SVGD direction
+        is that of the particles' r coordinates in the subspace, with this
+        sampler's kernel and bandwidth rule there (the median is that of the
+        projected distances), lifted back; the orthogonal complement stays
+        where it was drawn.  A learned basis is refreshed eagerly, between the
+        (captured) iterations, from the scores of the current particles; the
+        Projection carries basis, eigenvalues, captured and refreshes
+        afterwards.  ksd_every still measures in the full d dimensions, on an
+        engine of its own with its own bandwidth there."""
         if order not in ("sequential", "jacobi"):
             raise ValueError("order must be 'sequential' or 'jacobi'")
         if ksd_every is not None:
@@ -78,6 +92,16 @@ class Sampler(object):
         if rule is not None and order != "jacobi":
             raise ValueError("adagrad needs order='jacobi': the sequential sweeps move their "
                              "rows inside the sweep kernels, which take fixed steps")
+        if project is not None:
+            if not isinstance(project, Projection):
+                raise ValueError("project must be None or a dsvgd.Projection, got %r" % (project,))
+            if order != "jacobi":
+                raise ValueError("project needs order='jacobi': the subspace step moves all "
+                                 "particles together")
+            if rule is not None:
+                raise ValueError("project refuses adagrad: a per-entry history has no meaning "
+                                 "in coordinates that rotate with the basis")
+            project.check(self._d)
         self.diagnostics = None
         dev = N.require_gpu(device if device is not None else "cuda")
         q = Normal(0, 1)
@@ -91,9 +115,12 @@ class Sampler(object):
         median = self._rbf.median
         # (ksd() reads K . Xc, which only the two-operand phi_mm leaves behind)
         form = "w" if ksd_every is None else "xs"
+        # (a projected run interacts on its own r-wide engine)
+        peng = project.begin(n, d, self._rbf, dev) if project is not None else None
         engine = (PhiEngine(n, d, device=dev, phi_form=form, kernel=self._rbf)
-                  if (order == "jacobi" or median) else None)
-        state = engine.state if engine is not None else SelectState(dev)
+                  if ((order == "jacobi" or median) and peng is None) else None)
+        state = (peng.engine.state if peng is not None
+                 else engine.state if engine is not None else SelectState(dev))
         if not median:
             N.call("dsvgd_set_bandwidth", state.ptr, float(self._rbf.h), N.stream(dev))
         target = self._target
@@ -105,7 +132,9 @@ class Sampler(object):
 
         def iteration():
             target.score(X, S)
-            if order == "jacobi":
+            if peng is not None:
+                peng.step(X, S, step_size, h=None if median else self._rbf.h)
+            elif order == "jacobi":
                 if ada is not None:
                     engine.step(X, S, X_own=X, step=step_size,
                                 h=None if median else self._rbf.h, adagrad=ada)
@@ -132,7 +161,7 @@ class Sampler(object):
         if records:
             kout = torch.empty(len(records), 4, dtype=torch.float64, device=dev)
             kh = torch.empty(len(records), dtype=torch.float32, device=dev)
-            fused = order == "jacobi" and d > PhiEngine.DIRECT_MAX_D
+            fused = order == "jacobi" and d > PhiEngine.DIRECT_MAX_D and peng is None
             keng = engine if fused else PhiEngine(n, d, device=dev, kernel=self._rbf)
             Sk = S if fused else torch.empty_like(S)
             h_fixed = None if median else self._rbf.h
@@ -152,6 +181,9 @@ class Sampler(object):
             rec = bool(records) and l % ksd_every == 0
             if rec and not fused:
                 record(l, True)
+            if peng is not None and project.due(l):
+                target.score(X, S)      # (the iteration's own window; it moves after the step)
+                project.refresh(peng, X, S, l)
             step()
             if rec and fused:
                 record(l, False)

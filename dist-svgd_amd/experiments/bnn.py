@@ -14,6 +14,13 @@ fixed size over all the data by default, Liu & Wang's AdaGrad steps with
 
     python experiments/bnn.py --adagrad --stepsize 1e-3 --batch 100
 
+`--project R` runs projected SVGD (dsvgd.Projection): the particles interact
+in the R leading directions of the gradient of log(p / N(0, I)), relearned
+every `--project-every` iterations; the share of that gradient's second moment
+the subspace captures is printed for each refresh:
+
+    python experiments/bnn.py --project 16 --project-every 25
+
 Every `--every` iterations the test
 RMSE of the particle-mean prediction and the mean test log-likelihood of the
 particle mixture are printed (dsvgd.metrics.bnn_rmse / bnn_loglik, from the
@@ -45,17 +52,23 @@ def synthetic_regression(N=1000, p=8, seed=0, test_fraction=0.1):
 
 
 def run(nparticles, niter, stepsize, every, hidden=50, rows=1000, p=8, seed=0, device="cuda:0",
-        out=print, adagrad=False, batch=None):
+        out=print, adagrad=False, batch=None, project=None, project_every=10):
     """Runs the experiment; returns the recorded curve as a list of dicts
     (iteration, rmse, loglik) and the final KSD.  adagrad: True or a
-    dsvgd.AdaGrad for AdaGrad steps; batch: rows per minibatch (None: all)."""
+    dsvgd.AdaGrad for AdaGrad steps; batch: rows per minibatch (None: all);
+    project: the rank of projected SVGD (None: plain SVGD), its basis
+    relearned every project_every iterations."""
     x_train, y_train, x_test, y_test = synthetic_regression(rows, p, seed)
     target = dsvgd.targets.BayesianNN(x_train, y_train, hidden=hidden, batch=batch)
     d = target.d
     torch.manual_seed(seed)
     sampler = dsvgd.Sampler(d, target, dsvgd.RBF("median"))
+    proj = dsvgd.Projection(rank=project, every=project_every) if project else None
     df = sampler.sample(nparticles, niter, stepsize, order="jacobi", device=device, verbose=False,
-                        adagrad=adagrad or None)
+                        adagrad=adagrad or None, project=proj)
+    if proj is not None:
+        for it, captured in proj.captured_history:
+            out("iteration %5d  basis refresh: rank %d captured %.4f" % (it, proj.rank, captured))
     hist = np.stack(df["value"].to_list()).reshape(niter + 1, nparticles, d)
     curve = []
     for it in sorted(set(range(0, niter + 1, every)) | {niter}):
@@ -83,9 +96,14 @@ def run(nparticles, niter, stepsize, every, hidden=50, rows=1000, p=8, seed=0, d
               help="AdaGrad-conditioned steps (Liu & Wang's rule)")
 @click.option('--batch', type=int, default=None,
               help='rows per minibatch (a cyclic window; default: all the data)')
-def cli(nparticles, niter, stepsize, every, hidden, rows, features, seed, adagrad, batch):
+@click.option('--project', type=int, default=None,
+              help='projected SVGD in a learned subspace of this rank (default: plain SVGD)')
+@click.option('--project-every', type=int, default=10,
+              help='relearn the subspace every k iterations')
+def cli(nparticles, niter, stepsize, every, hidden, rows, features, seed, adagrad, batch, project,
+        project_every):
     run(nparticles, niter, stepsize, every, hidden, rows, features, seed, adagrad=adagrad,
-        batch=batch)
+        batch=batch, project=project, project_every=project_every)
 
 
 if __name__ == "__main__":

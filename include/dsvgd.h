@@ -1266,6 +1266,40 @@ int dsvgd_mmd_finish(const float* P, int64_t n_total, int64_t n_first, int sym, 
                      int64_t force, float* rp, float* rq, float* witness, double* ws,
                      double* out, void* stream);
 
+/* ---- projected SVGD (csrc/project.hip) ---------------------------------------
+ * The three dense products around an r-wide SVGD step in the subspace spanned
+ * by the orthonormal columns of Psi (d x r, row-major, row stride ldpsi), for
+ * n particles X and their scores S (row-major, row strides >= d):
+ * 1 <= d <= 1024, 1 <= r <= min(d, 256), n >= 1.  All run on the exact f32
+ * MFMA (v_mfma_f32_32x32x2_f32), without atomics and with every sum in a fixed
+ * order: two calls give the same bits.
+ *
+ * dsvgd_proj_gram: H = (1/n) sum_i g_i g_i^T (d x d, row stride ldh), g_i =
+ * S_i + X_i (add_x != 0; rounded to f32 once) or S_i (add_x == 0; X is not
+ * read and may be null).  Only the tiles on and above the diagonal are
+ * computed; every entry is written together with its mirror image, so H is
+ * exactly symmetric.  The particles are split into dsvgd_proj_gram_slices(n, d)
+ * slices of whole 32-row chunks (none empty; one slice up to 256 particles, no
+ * accumulator chain longer than 8192), whose partial sums meet in slice order.
+ * workspace: dsvgd_proj_gram_workspace_bytes(n, d) bytes.
+ *
+ * dsvgd_proj_apply: Xr = X Psi and Sr = S Psi (n x r) in one launch; X and S
+ * are each read once.
+ *
+ * dsvgd_proj_lift: X += step . Phir Psi^T (Phir n x r); a non-null Phi_out
+ * (n x d, row stride ldo) is set to Phir Psi^T.  step == 0: X is neither read
+ * nor written (and may be null). */
+int64_t dsvgd_proj_gram_slices(int64_t n, int64_t d);
+size_t dsvgd_proj_gram_workspace_bytes(int64_t n, int64_t d);
+int dsvgd_proj_gram(const float* X, int64_t ldx, const float* S, int64_t lds, int64_t n, int64_t d,
+                    int add_x, void* workspace, float* H, int64_t ldh, void* stream);
+int dsvgd_proj_apply(const float* X, int64_t ldx, const float* S, int64_t lds, int64_t n,
+                     int64_t d, const float* Psi, int64_t ldpsi, int64_t r, float* Xr,
+                     int64_t ldxr, float* Sr, int64_t ldsr, void* stream);
+int dsvgd_proj_lift(const float* Phir, int64_t ldphi, const float* Psi, int64_t ldpsi, int64_t n,
+                    int64_t d, int64_t r, float step, float* X, int64_t ldx, float* Phi_out,
+                    int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
