@@ -7,7 +7,8 @@
 //   t_i = s_i.KS_i + (2/h)[ r_i a_i - s_i.KXc_i - xc_i.KS_i + b_i ]
 //         + (2d/h) r_i - (4/h^2) q_i,
 //   a_j = s_j.xc_j,  b_i = sum_{j != i} k_ij a_j,  q_i = sum_{j != i} k_ij D_ij.
-// KXc, KS, r are phi_mm's outputs; b and q are the one sweep over D below.
+// KXc, KS, r are phi_mm's outputs; b and q are one sweep over D: the shared
+// walker of dsweep.hpp with the payload below.
 //
 // For the inverse multiquadric k = u^beta, u = 1 + D/h (FAM = IMQ below), with
 // F = u^beta, G' = u^(beta-1), H' = u^(beta-2), c1 = -2 beta/h, c2 = 4 beta
@@ -19,24 +20,14 @@
 //
 // Everything is deterministic: no float atomics, every partial has a slot of
 // its own and every sum a fixed order.
-#include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "dsweep.hpp"
 
 namespace dsvgd {
 
-constexpr int kKsdPanel = 2048;       // 128 rows x 16 columns of D, contiguous
-constexpr int kKsdBlockTarget = 2048; // workgroups that fill 256 CUs 8 deep
-constexpr int kKsdRowsPerBlock = 64;  // rows of one finish / direct workgroup
 constexpr int kKsdDirectMaxD = 64;
 constexpr int kKsdDirectJ = 32;       // columns staged per chunk (direct form)
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // a[j] = s_j . xc_j for j < n, 0 for n <= j < n_pad (fp64 dot, one wave per row)
 __global__ __launch_bounds__(256) void ksd_a_kernel(const float* __restrict__ Y, int64_t ldy,
@@ -54,108 +45,90 @@ __global__ __launch_bounds__(256) void ksd_a_kernel(const float* __restrict__ Y,
   if (lane == 0) a[j] = (float)s;
 }
 
-// One panel's share of a thread: rows r0 (v0) and r0 + 64 (v1), four columns
-// from j0.  q += k D, b += k a_j per row; COLS: cv[0..3] = the two rows' k D
-// per column, cv[4..7] = their k a_i (the transposed tile's terms).  MASK:
-// entries with a row or column past the matrix (+inf pads: exp(-inf) inf is
-// NaN) or on the diagonal contribute exactly 0.
-// FAM = IMQ: k -> G' = u^pw (pw = beta - 1, scale = 1/h) and k D -> H' D =
-// u^(pw-1) D.
-template <bool MASK, bool COLS, int FAM = kFamRBF>
-__device__ __forceinline__ void ksd_panel(const f32x4 v0, const f32x4 v1, const f32x4 a4,
-                                          float scale, int64_t g0, int64_t j0, bool rv0, bool rv1,
-                                          int64_t n, float ai0, float ai1, float& q0, float& b0,
-                                          float& q1, float& b1, float* cv, float pw = 0.f) {
+// The sweep's payload (dsweep.hpp): quantity 0 is q += k D, quantity 1 is
+// b += k a_j, with a_j the panel's extra load; cv[0..3] = the two rows' k D
+// per column, cv[4..7] = their k a_i (the transposed tile's terms, weights
+// ai0, ai1 of the thread's rows).  Masked entries are exact zeros, not
+// products: exp(-inf) inf is NaN.  FAM = IMQ: k -> G' = u^pw (pw = beta - 1,
+// scale = 1/h) and k D -> H' D = u^(pw-1) D.
+template <int FAM>
+struct KsdPayload {
+  using extra = f32x4;
+  const float* a;
+  float scale, pw, ai0, ai1;
+  __device__ KsdPayload(const float* a_, const dsvgd_select_state* st, float pw_)
+      : a(a_), scale(FAM == kFamIMQ ? st->inv_h : -st->inv_h * kLog2e), pw(pw_), ai0(0.f),
+        ai1(0.f) {}
+  __device__ void rows(int64_t i0) {
+    ai0 = a[i0];
+    ai1 = a[i0 + 64];
+  }
+  __device__ f32x4 load(int64_t c, int cq) const {
+    return *reinterpret_cast<const f32x4*>(a + 16 * c + 4 * cq);
+  }
+  __device__ bool edge(int64_t) const { return false; }
+
+  template <bool MASK, bool COLS>
+  __device__ __forceinline__ void panel(const f32x4 v0, const f32x4 v1, const f32x4 a4, int64_t,
+                                        int64_t g0, int64_t j0, bool rv0, bool rv1, int64_t n,
+                                        float& q0, float& b0, float& q1, float& b1,
+                                        float* cv) const {
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float k0, k1, kd0, kd1;
-    if constexpr (FAM == kFamIMQ) {
-      const float l0 = __builtin_amdgcn_logf(fmaf(v0[e], scale, 1.f));
-      const float l1 = __builtin_amdgcn_logf(fmaf(v1[e], scale, 1.f));
-      k0 = __builtin_amdgcn_exp2f(pw * l0);
-      k1 = __builtin_amdgcn_exp2f(pw * l1);
-      kd0 = __builtin_amdgcn_exp2f((pw - 1.f) * l0) * v0[e];
-      kd1 = __builtin_amdgcn_exp2f((pw - 1.f) * l1) * v1[e];
-    } else {
-      k0 = __builtin_amdgcn_exp2f(v0[e] * scale);
-      k1 = __builtin_amdgcn_exp2f(v1[e] * scale);
-      kd0 = k0 * v0[e];
-      kd1 = k1 * v1[e];
-    }
-    if (MASK) {
-      const int64_t j = j0 + e;
-      const bool ok0 = rv0 && j < n && j != g0;
-      const bool ok1 = rv1 && j < n && j != g0 + 64;
-      k0 = ok0 ? k0 : 0.f;
-      kd0 = ok0 ? kd0 : 0.f;
-      k1 = ok1 ? k1 : 0.f;
-      kd1 = ok1 ? kd1 : 0.f;
-    }
-    q0 += kd0;
-    q1 += kd1;
-    b0 = fmaf(k0, a4[e], b0);
-    b1 = fmaf(k1, a4[e], b1);
-    if (COLS) {
-      cv[e] = kd0 + kd1;
-      cv[4 + e] = fmaf(k0, ai0, k1 * ai1);
+    for (int e = 0; e < 4; ++e) {
+      float k0, k1, kd0, kd1;
+      if constexpr (FAM == kFamIMQ) {
+        const float l0 = __builtin_amdgcn_logf(fmaf(v0[e], scale, 1.f));
+        const float l1 = __builtin_amdgcn_logf(fmaf(v1[e], scale, 1.f));
+        k0 = __builtin_amdgcn_exp2f(pw * l0);
+        k1 = __builtin_amdgcn_exp2f(pw * l1);
+        kd0 = __builtin_amdgcn_exp2f((pw - 1.f) * l0) * v0[e];
+        kd1 = __builtin_amdgcn_exp2f((pw - 1.f) * l1) * v1[e];
+      } else {
+        k0 = __builtin_amdgcn_exp2f(v0[e] * scale);
+        k1 = __builtin_amdgcn_exp2f(v1[e] * scale);
+        kd0 = k0 * v0[e];
+        kd1 = k1 * v1[e];
+      }
+      if (MASK) {
+        const int64_t j = j0 + e;
+        const bool ok0 = rv0 && j < n && j != g0;
+        const bool ok1 = rv1 && j < n && j != g0 + 64;
+        k0 = ok0 ? k0 : 0.f;
+        kd0 = ok0 ? kd0 : 0.f;
+        k1 = ok1 ? k1 : 0.f;
+        kd1 = ok1 ? kd1 : 0.f;
+      }
+      q0 += kd0;
+      q1 += kd1;
+      b0 = fmaf(k0, a4[e], b0);
+      b1 = fmaf(k1, a4[e], b1);
+      if (COLS) {
+        cv[e] = kd0 + kd1;
+        cv[4 + e] = fmaf(k0, ai0, k1 * ai1);
+      }
     }
   }
-}
+};
 
-// the four lanes that share a row hold its partial sums
-__device__ __forceinline__ float quad_sum(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  return v;
-}
-
-// Full panel layout: workgroup (I, z) walks the 16-column panels of row tile
-// I in column slice z; thread t reads two 16-byte pieces per panel (rows t/4
-// and t/4 + 64, columns 4 (t % 4) ..), a wave 1 KiB contiguous per load.
-// P[z][0][i] = q, P[z][1][i] = b of the slice.  No LDS.
+// The sweep in the full panel layout (sweep_full): P[z][0][i] = q, P[z][1][i]
+// = b of column slice z, for the rows [row0, row0 + m) of a row block.
 template <int FAM = kFamRBF>
 __global__ __launch_bounds__(256) void ksd_rows_full_kernel(
     const float* __restrict__ D, int64_t n_pad, const float* __restrict__ a, int64_t row0,
     int64_t m, int64_t n, const dsvgd_select_state* __restrict__ st, int parts,
     float* __restrict__ P, int64_t m_pad, float pw = 0.f) {
-  const int t = threadIdx.x, cq = t & 3, r0 = t >> 2;
-  const int64_t I = blockIdx.x;
-  const int z = blockIdx.y;
-  const int64_t pcols = n_pad >> 4;
-  const int64_t c0 = pcols * z / parts, c1 = pcols * (z + 1) / parts;
-  const float scale = FAM == kFamIMQ ? st->inv_h : -st->inv_h * kLog2e;
-  const int64_t i0 = I * 128 + r0;
-  const bool rv0 = i0 < m, rv1 = i0 + 64 < m;
-  const int64_t g0 = row0 + i0;          // the row's own column
-  const int64_t gt = row0 + I * 128;     // the tile's first own column
-  const bool row_edge = (I + 1) * 128 > m;
-  const f32x4* Dp = reinterpret_cast<const f32x4*>(D) + I * pcols * (kKsdPanel / 4) + t;
-  float q0 = 0.f, b0 = 0.f, q1 = 0.f, b1 = 0.f;
-#pragma unroll 2
-  for (int64_t c = c0; c < c1; ++c) {
-    const f32x4 v0 = Dp[c * (kKsdPanel / 4)];
-    const f32x4 v1 = Dp[c * (kKsdPanel / 4) + 256];
-    const f32x4 a4 = *reinterpret_cast<const f32x4*>(a + 16 * c + 4 * cq);
-    const int64_t j0 = 16 * c + 4 * cq;
-    const bool edge = row_edge || 16 * c + 16 > n || (16 * c + 15 >= gt && 16 * c <= gt + 127);
-    if (edge)
-      ksd_panel<true, false, FAM>(v0, v1, a4, scale, g0, j0, rv0, rv1, n, 0.f, 0.f, q0, b0, q1, b1,
-                                  nullptr, pw);
-    else
-      ksd_panel<false, false, FAM>(v0, v1, a4, scale, g0, j0, rv0, rv1, n, 0.f, 0.f, q0, b0, q1,
-                                   b1, nullptr, pw);
-  }
-  q0 = quad_sum(q0);
-  q1 = quad_sum(q1);
-  b0 = quad_sum(b0);
-  b1 = quad_sum(b1);
-  if (cq == 0) {
-    float* Pz = P + (int64_t)z * 2 * m_pad;
-    Pz[i0] = q0;
-    Pz[i0 + 64] = q1;
-    Pz[m_pad + i0] = b0;
-    Pz[m_pad + i0 + 64] = b1;
-  }
+  KsdPayload<FAM> pl(a, st, pw);
+  sweep_full(D, SweepGeom<int64_t>{n_pad, row0, m, n, m_pad}, parts, P, pl);
+}
+
+// ... and in the symmetric layout (sweep_sym): the column sums carry the
+// weights a_i of the stored rows.
+template <int FAM = kFamRBF>
+__global__ __launch_bounds__(256) void ksd_rows_sym_kernel(
+    const float* __restrict__ D, int64_t n_pad, const float* __restrict__ a, int64_t n,
+    const dsvgd_select_state* __restrict__ st, int rparts, float* __restrict__ P, float pw = 0.f) {
+  KsdPayload<FAM> pl(a, st, pw);
+  sweep_sym(D, n_pad, n, rparts, P, pl);
 }
 
 // gate[0] = 1 if an owned row's kernel mass r_i = sum_z rowsum[z][i] is below
@@ -178,103 +151,8 @@ __global__ __launch_bounds__(256) void ksd_gate_kernel(const float* __restrict__
   if (threadIdx.x == 0) gate[0] = flag ? 1.f : 0.f;
 }
 
-// Eight per-thread values (two quantities x four columns) summed over the 16
-// lanes of a wave that hold the same columns (lane bits 2..5), each step
-// trading half of what is left: 8 cross-lane moves instead of 32.  Returns,
-// in every lane, the wave's sum of quantity (lane >> 2) & 1 for the column
-// 2 ((lane >> 3) & 1) + ((lane >> 4) & 1) of the lane's quad.
-__device__ __forceinline__ float ksd_col_reduce(const float* v, int lane) {
-  const bool bA = lane & 4, bB = lane & 8, bC = lane & 16;
-  float w[4], x[2];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float keep = bA ? v[k + 4] : v[k], send = bA ? v[k] : v[k + 4];
-    w[k] = keep + __shfl_xor(send, 4, 64);
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const float keep = bB ? w[k + 2] : w[k], send = bB ? w[k] : w[k + 2];
-    x[k] = keep + __shfl_xor(send, 8, 64);
-  }
-  const float keep = bC ? x[1] : x[0], send = bC ? x[0] : x[1];
-  float y = keep + __shfl_xor(send, 16, 64);
-  y += __shfl_xor(y, 32, 64);
-  return y;
-}
-
-// Symmetric layout (only tiles (I, J >= I) stored): workgroup (I, z) walks
-// slice z of the stored tiles of tile row I.  Row sums as above into slot z;
-// an off-diagonal tile's column sums (the terms of the unwritten tile (J, I):
-// weights a_i, i in I) go to slot rparts + I at rows of J -- one slot per
-// stored tile row, summed by the finish for I < J in order.  The diagonal
-// tile counts once, without its diagonal.
-template <int FAM = kFamRBF>
-__global__ __launch_bounds__(256) void ksd_rows_sym_kernel(
-    const float* __restrict__ D, int64_t n_pad, const float* __restrict__ a, int64_t n,
-    const dsvgd_select_state* __restrict__ st, int rparts, float* __restrict__ P, float pw = 0.f) {
-  __shared__ float red[4][2][128];
-  const int t = threadIdx.x, cq = t & 3, r0 = t >> 2, lane = t & 63, wv = t >> 6;
-  const int64_t I = blockIdx.x;
-  const int z = blockIdx.y;
-  const int64_t T = n_pad >> 7, pcols = n_pad >> 4, len = T - I;
-  const int64_t J0 = I + len * z / rparts, J1 = I + len * (z + 1) / rparts;
-  const float scale = FAM == kFamIMQ ? st->inv_h : -st->inv_h * kLog2e;
-  const int64_t i0 = I * 128 + r0;
-  const bool rv0 = i0 < n, rv1 = i0 + 64 < n;
-  const float ai0 = a[i0], ai1 = a[i0 + 64];
-  const bool pads = n < n_pad;
-  const f32x4* Dp = reinterpret_cast<const f32x4*>(D) + I * pcols * (kKsdPanel / 4) + t;
-  float* Pc = P + (int64_t)(rparts + I) * 2 * n_pad;
-  // the lane's result of ksd_col_reduce: quantity and column within a panel
-  const int cqty = (lane >> 2) & 1;
-  const int ccol = 4 * cq + 2 * ((lane >> 3) & 1) + ((lane >> 4) & 1);
-  float q0 = 0.f, b0 = 0.f, q1 = 0.f, b1 = 0.f;
-  for (int64_t J = J0; J < J1; ++J) {
-    const bool diag = J == I;
-    const bool edge = diag || (pads && (I == T - 1 || J == T - 1));
-#pragma unroll 2
-    for (int p = 0; p < 8; ++p) {
-      const int64_t c = J * 8 + p;
-      const f32x4 v0 = Dp[c * (kKsdPanel / 4)];
-      const f32x4 v1 = Dp[c * (kKsdPanel / 4) + 256];
-      const f32x4 a4 = *reinterpret_cast<const f32x4*>(a + 16 * c + 4 * cq);
-      const int64_t j0 = 16 * c + 4 * cq;
-      float cv[8];
-      if (edge)
-        ksd_panel<true, true, FAM>(v0, v1, a4, scale, i0, j0, rv0, rv1, n, ai0, ai1, q0, b0, q1, b1,
-                                   cv, pw);
-      else
-        ksd_panel<false, true, FAM>(v0, v1, a4, scale, i0, j0, rv0, rv1, n, ai0, ai1, q0, b0, q1,
-                                    b1, cv, pw);
-      if (!diag) {  // block-uniform
-        const float y = ksd_col_reduce(cv, lane);
-        if (lane < 32) red[wv][cqty][16 * p + ccol] = y;
-      }
-    }
-    if (!diag) {
-      __syncthreads();
-      const int qty = t >> 7, col = t & 127;
-      const float s = ((red[0][qty][col] + red[1][qty][col]) + red[2][qty][col]) + red[3][qty][col];
-      Pc[(int64_t)qty * n_pad + J * 128 + col] = s;
-      __syncthreads();
-    }
-  }
-  q0 = quad_sum(q0);
-  q1 = quad_sum(q1);
-  b0 = quad_sum(b0);
-  b1 = quad_sum(b1);
-  if (cq == 0) {
-    float* Pz = P + (int64_t)z * 2 * n_pad;
-    Pz[i0] = q0;
-    Pz[i0 + 64] = q1;
-    Pz[n_pad + i0] = b0;
-    Pz[n_pad + i0 + 64] = b1;
-  }
-}
-
-// t_i, u_ii for 64 rows per workgroup.  First the rows' q and b: wave w adds
-// the slots w, w + 4, .. of 64 consecutive rows (coalesced), the four wave
-// sums are added in order.  Then one wave per row: the split-K slices summed
+// t_i, u_ii for 64 rows per workgroup.  First the rows' q and b from the
+// sweep's slots (slot_sums).  Then one wave per row: the split-K slices summed
 // in slice order in fp32 as phi_finish does, the five dot products in fp64.
 // ws[2 blk], ws[2 blk + 1] = the workgroup's sums of t and u_ii in row order.
 // FAM = IMQ: KY is the F run's [F Xc | F S], KG the G' run's [G' Xc | G' S]
@@ -307,25 +185,8 @@ __global__ __launch_bounds__(256) void ksd_finish_kernel(
   [[maybe_unused]] const float beta = ia.beta;
   __shared__ double shq[4][64], shb[4][64], sht[4][2];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int64_t ib = (int64_t)blockIdx.x * kKsdRowsPerBlock;
-  {
-    // symmetric layout: slots [0, rparts) the row sums, then one per stored
-    // tile row I < this row's tile (the 64 rows share a tile)
-    const int nslots = sym ? parts - (int)(m_pad >> 7) + (int)(ib >> 7) : parts;
-    const int64_t i = ib + lane;
-    double q = 0.0, b = 0.0;
-    if (i < m) {
-#pragma unroll 4
-      for (int sl = wv; sl < nslots; sl += 4) {
-        const float* Ps = P + (int64_t)sl * 2 * m_pad;
-        q += (double)Ps[i];
-        b += (double)Ps[m_pad + i];
-      }
-    }
-    shq[wv][lane] = q;
-    shb[wv][lane] = b;
-  }
-  __syncthreads();
+  const int64_t ib = (int64_t)blockIdx.x * kSweepRowsPerBlock;
+  slot_sums(P, m_pad, m, ib, sym, parts, shq, shb);
   // RBF: g = 2/h (and g^2 = 4/h^2 below); IMQ: c1 (and c2) in their places
   const double ih = (double)st->inv_h, g = FAM == kFamIMQ ? -2.0 * (double)beta * ih : 2.0 * ih;
   double wt = 0.0, wu = 0.0;
@@ -365,8 +226,7 @@ __global__ __launch_bounds__(256) void ksd_finish_kernel(
     ss = wave_sum_f64(ss);
     float r = 0.f;
     for (int zz = 0; zz < splits; ++zz) r += rowsum[(int64_t)zz * m_pad + i];
-    const double q = ((shq[0][rr] + shq[1][rr]) + shq[2][rr]) + shq[3][rr];
-    const double b = ((shb[0][rr] + shb[1][rr]) + shb[2][rr]) + shb[3][rr];
+    const double q = sum4(shq, rr), b = sum4(shb, rr);
     const double rd = (double)r, dd = (double)d;
     double ti;
     if constexpr (FAM == kFamIMQ)
@@ -387,29 +247,13 @@ __global__ __launch_bounds__(256) void ksd_finish_kernel(
   if (t < 2) ws[2 * (int64_t)blockIdx.x + t] = ((sht[0][t] + sht[1][t]) + sht[2][t]) + sht[3][t];
 }
 
-// the second level: thread t adds the workgroup sums t, t + 256, .. in order,
-// then a fixed halving tree; out = [off, diag, V, U]
+// the second level (block_totals); out = [off, diag, V, U]
 __global__ __launch_bounds__(256) void ksd_reduce_kernel(const double* __restrict__ ws, int64_t nb,
                                                          int64_t n, double* __restrict__ out) {
-  __shared__ double sh[2][256];
-  const int t = threadIdx.x;
-  double s0 = 0.0, s1 = 0.0;
-  for (int64_t b = t; b < nb; b += 256) {
-    s0 += ws[2 * b];
-    s1 += ws[2 * b + 1];
-  }
-  sh[0][t] = s0;
-  sh[1][t] = s1;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (t < h) {
-      sh[0][t] += sh[0][t + h];
-      sh[1][t] += sh[1][t + h];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    const double off = sh[0][0], diag = sh[1][0], nn = (double)n;
+  double tot[2];
+  block_totals<2>(ws, nb, tot);
+  if (threadIdx.x == 0) {
+    const double off = tot[0], diag = tot[1], nn = (double)n;
     out[0] = off;
     out[1] = diag;
     out[2] = (off + diag) / (nn * nn);
@@ -429,7 +273,7 @@ __global__ __launch_bounds__(256) void ksd_direct_kernel(
   __shared__ float xj[kKsdDirectJ * kKsdDirectMaxD], sj[kKsdDirectJ * kKsdDirectMaxD];  // [jj][c]
   __shared__ double part[4][64];
   const int t = threadIdx.x, r = t & 63, g = t >> 6;
-  const int64_t ib = (int64_t)blockIdx.x * kKsdRowsPerBlock, i = ib + r;
+  const int64_t ib = (int64_t)blockIdx.x * kSweepRowsPerBlock, i = ib + r;
   for (int e = t; e < 64 * d; e += 256) {
     const int c = e >> 6, rr = e & 63;
     const bool ok = ib + rr < m;
@@ -498,10 +342,6 @@ __global__ __launch_bounds__(256) void ksd_direct_kernel(
   }
 }
 
-static int64_t ksd_row_parts(int64_t tiles, int64_t cap) {
-  return std::max<int64_t>(1, std::min<int64_t>((kKsdBlockTarget + tiles - 1) / tiles, cap));
-}
-
 static bool a16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 }  // namespace dsvgd
@@ -515,14 +355,14 @@ int64_t dsvgd_ksd_parts(int64_t m, int64_t n, int sym) {
   const int64_t n_pad = roundup(n, 128), m_pad = roundup(m, 128);
   if (sym) {
     const int64_t T = n_pad / 128;
-    return ksd_row_parts(T, T) + T;
+    return row_parts(T, T) + T;
   }
   // at least eight panels (128 columns) per slice
-  return ksd_row_parts(m_pad / 128, n_pad / 128);
+  return row_parts(m_pad / 128, n_pad / 128);
 }
 
 size_t dsvgd_ksd_workspace_doubles(int64_t m) {
-  return m > 0 ? 2 * (size_t)((m + kKsdRowsPerBlock - 1) / kKsdRowsPerBlock) : 0;
+  return m > 0 ? 2 * (size_t)((m + kSweepRowsPerBlock - 1) / kSweepRowsPerBlock) : 0;
 }
 
 int dsvgd_ksd_gate(const float* rowsum, int64_t splits, int64_t m, int64_t n, float* gate,
@@ -596,7 +436,7 @@ int dsvgd_ksd_finish(const float* KY, int64_t ldk, const float* rowsum, int64_t 
   DSVGD_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 7) == 0,
                 "ws and out must be 8-byte aligned");
   const int64_t m_pad = roundup(m, 128);
-  const int64_t nb = (m + kKsdRowsPerBlock - 1) / kKsdRowsPerBlock;
+  const int64_t nb = (m + kSweepRowsPerBlock - 1) / kSweepRowsPerBlock;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ksd_finish_kernel<kFamRBF>, dim3((unsigned)nb), dim3(256), 0, s, KY, ldk,
                      rowsum, (int)splits, Y, ldy, dp, d, row0, m, m_pad, st, sym ? 1 : 0,
@@ -624,7 +464,7 @@ int dsvgd_ksd_finish_imq(const float* KF, int64_t ldkf, const float* KG, int64_t
   DSVGD_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 7) == 0,
                 "ws and out must be 8-byte aligned");
   const int64_t m_pad = roundup(m, 128);
-  const int64_t nb = (m + kKsdRowsPerBlock - 1) / kKsdRowsPerBlock;
+  const int64_t nb = (m + kSweepRowsPerBlock - 1) / kSweepRowsPerBlock;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ksd_finish_kernel<kFamIMQ>, dim3((unsigned)nb), dim3(256), 0, s, KF, ldkf,
                      rowsum, (int)splits, Y, ldy, dp, d, row0, m, m_pad, st, sym ? 1 : 0,
@@ -651,7 +491,7 @@ int dsvgd_ksd_direct_kern(const float* Y, int64_t ldy, int64_t dp, int64_t d, in
   DSVGD_REQUIRE(dp >= d && ldy >= 2 * dp, "dp >= d and ldy >= 2 dp");
   DSVGD_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 7) == 0,
                 "ws and out must be 8-byte aligned");
-  const int64_t nb = (m + kKsdRowsPerBlock - 1) / kKsdRowsPerBlock;
+  const int64_t nb = (m + kSweepRowsPerBlock - 1) / kSweepRowsPerBlock;
   hipStream_t s = (hipStream_t)stream;
   if (kern.family == DSVGD_KERNEL_IMQ)
     hipLaunchKernelGGL(ksd_direct_kernel<kFamIMQ>, dim3((unsigned)nb), dim3(256), 0, s, Y, ldy, dp,

@@ -173,6 +173,26 @@ class AdaGradState(object):
         self.G.fill_(-1.0)
 
 
+class _DiagBuffers(dict):
+    """The kept workspaces of a D-sweep diagnostic (PhiEngine.ksd, .mmd): what
+    identifies them (key, parts) and device vectors by name, given as element
+    counts per dtype."""
+
+    def __init__(self, device, f64, f32, **meta):
+        super().__init__(**meta)
+        for dtype, counts in ((torch.float64, f64), (torch.float32, f32)):
+            for name, count in counts.items():
+                self[name] = torch.empty(int(count), dtype=dtype, device=device)
+
+    def result(self, out):
+        """The "out" vector: a copy, or `out` itself after it was written."""
+        if out is None:
+            return self["out"].clone()
+        assert out.shape == self["out"].shape and out.dtype == torch.float64
+        out.copy_(self["out"])
+        return out
+
+
 class PhiEngine(object):
     timer = None
     # median select: bracketed (sample -> [lo, hi] -> candidates) when the
@@ -1031,16 +1051,14 @@ class PhiEngine(object):
         sym = int(self.sym)
         key = (direct, sym, self.m)
         if self._ksd is None or self._ksd["key"] != key:
-            f64 = dict(dtype=torch.float64, device=self.device)
-            f32 = dict(dtype=torch.float32, device=self.device)
-            W = dict(key=key, out=torch.empty(4, **f64), rows=torch.empty(self.m, **f32),
-                     ws=torch.empty(int(lib.dsvgd_ksd_workspace_doubles(self.m)), **f64))
-            if not direct:
-                W["parts"] = int(lib.dsvgd_ksd_parts(self.m, self.n, sym))
-                W["P"] = torch.empty(W["parts"] * 2 * self.m_pad, **f32)
-                W["a"] = torch.empty(self.n_pad, **f32)
-                W["gate"] = torch.zeros(1, **f32)
-            self._ksd = W
+            f64 = dict(out=4, ws=lib.dsvgd_ksd_workspace_doubles(self.m))
+            if direct:
+                self._ksd = _DiagBuffers(self.device, f64, dict(rows=self.m), key=key)
+            else:
+                parts = int(lib.dsvgd_ksd_parts(self.m, self.n, sym))
+                f32 = dict(rows=self.m, P=parts * 2 * self.m_pad, a=self.n_pad, gate=1)
+                self._ksd = _DiagBuffers(self.device, f64, f32, key=key, parts=parts)
+                self._ksd["gate"].zero_()
         W = self._ksd
         if direct:
             with span(self.timer, "ksd_direct"):
@@ -1075,11 +1093,7 @@ class PhiEngine(object):
                            self.splits, N.ptr(self.Y), self.ldy, self.dp, self.d, self.row0,
                            self.m, self.n, self.state.ptr, sym, W["parts"], N.ptr(W["P"]),
                            N.ptr(W["rows"]), N.ptr(W["ws"]), N.ptr(W["out"]), s)
-        if out is None:
-            out = W["out"].clone()
-        else:
-            assert out.shape == (4,) and out.dtype == torch.float64
-            out.copy_(W["out"])
+        out = W.result(out)
         return (out, W["rows"].clone()) if rows else out
 
     # --------------------------------------------------------------- MMD --
@@ -1115,14 +1129,10 @@ class PhiEngine(object):
         force = 0 if parts is None else int(parts)
         key = (sym, force)
         if self._mmd is None or self._mmd["key"] != key:
-            f64 = dict(dtype=torch.float64, device=self.device)
-            f32 = dict(dtype=torch.float32, device=self.device)
-            np_ = int(lib.dsvgd_mmd_parts(self.n, sym, force))
-            self._mmd = dict(key=key, parts=np_, out=torch.empty(5, **f64),
-                             P=torch.empty(np_ * 2 * self.n_pad, **f32),
-                             rp=torch.empty(self.n, **f32), rq=torch.empty(self.n, **f32),
-                             witness=torch.empty(self.n, **f32),
-                             ws=torch.empty(int(lib.dsvgd_mmd_workspace_doubles(self.n)), **f64))
+            parts = int(lib.dsvgd_mmd_parts(self.n, sym, force))
+            f64 = dict(out=5, ws=lib.dsvgd_mmd_workspace_doubles(self.n))
+            f32 = dict(P=parts * 2 * self.n_pad, rp=self.n, rq=self.n, witness=self.n)
+            self._mmd = _DiagBuffers(self.device, f64, f32, key=key, parts=parts)
         W = self._mmd
         with span(self.timer, "mmd_rows"):
             N.call("dsvgd_mmd_rows", N.ptr(self.D), self.n_pad, self.n, n_first, self.state.ptr,
@@ -1131,11 +1141,7 @@ class PhiEngine(object):
             N.call("dsvgd_mmd_finish", N.ptr(W["P"]), self.n, n_first, sym, W["parts"], force,
                    N.ptr(W["rp"]), N.ptr(W["rq"]), N.ptr(W["witness"]), N.ptr(W["ws"]),
                    N.ptr(W["out"]), s)
-        if out is None:
-            out = W["out"].clone()
-        else:
-            assert out.shape == (5,) and out.dtype == torch.float64
-            out.copy_(W["out"])
+        out = W.result(out)
         if rows:
             return out, W["rp"].clone(), W["rq"].clone(), W["witness"].clone()
         return out

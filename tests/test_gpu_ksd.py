@@ -168,8 +168,14 @@ def test_ksd_direct_d2():
     _check(out, rows, ksd_reference(X, Sg.cpu().numpy(), median_h64(X)))
 
 
-def test_ksd_row_block():
-    n, d, m, row0 = 513, 64, 256, 128
+@pytest.mark.parametrize("m,row0", [(256, 128), (70, 37), (200, 313)])
+def test_ksd_row_block(m, row0):
+    """The full-layout walk's row-block geometry: a tile-aligned block; one
+    ragged tile whose diagonal falls inside a 4-column vector load and across
+    a panel edge (the upper 64 rows mostly invalid); a block that ends at row
+    n, so its diagonal panels are also those with the +inf pads, its second
+    tile ragged."""
+    n, d = 513, 64
     X, target = _problem(n, d)
     Xg, Sg = _scores(X, target)
     h = float(np.float32(median_h64(X)))
