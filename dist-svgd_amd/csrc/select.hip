@@ -503,6 +503,7 @@ int dsvgd_radix_hist(const float* D, int64_t count, const float* cand, int pass,
   DSVGD_REQUIRE(sym_npad == 0 || (sym_npad % 128 == 0 && count == sym_npad * sym_npad),
                 "sym_npad: count must be sym_npad^2 (a square panel-layout matrix)");
   int64_t blocks = (count / 4 + 255) / 256;
+  if (blocks < 1) blocks = 1;  // count < 4: the scalar tail alone
   if (blocks > 4096) blocks = 4096;
   if (cand && blocks < 1024) blocks = 1024;  // candidate slots: one wave each, grid-stride
   hipLaunchKernelGGL(radix_hist_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, D, count,

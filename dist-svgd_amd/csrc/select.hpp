@@ -20,20 +20,28 @@ enum SelMode { kSelNone = 0, kSelHist = 1, kSelBracket = 2 };
 
 // Per-lane digit-1 histogram with an 8-bin register window (a tile's
 // distances cluster within a factor 2-4): packed 8 x 8-bit counters per lane,
-// out-of-window keys go to the LDS histogram.  Counts per lane <= 128.
+// out-of-window keys go to the LDS histogram.  A counter counts VALUES, one
+// per add(); the weight (1, or 2 for a mirrored tile -- wave-uniform for the
+// life of a WindowHist, fixed by init()) multiplies the wave's sums in
+// flush().  A lane adds at most 128 values between init() and flush() (the
+// 64 x 128 sub-tile of a sqdist_x3w_kernel wave), all of which may fall into
+// one bin (identical or equidistant particles): 128 <= 255 fits a counter,
+// 128 x weight 2 = 256 would not.
 struct WindowHist {
   uint64_t packed = 0;
   int base = 0;
-  __device__ __forceinline__ void init(float first) {
+  uint32_t weight = 1u;
+  __device__ __forceinline__ void init(float first, uint32_t w) {
     base = __builtin_amdgcn_readfirstlane((int)(__float_as_uint(first) >> 21)) - 3;
+    weight = w;
   }
-  __device__ __forceinline__ void add(float v, uint32_t w, uint32_t* shist) {
+  __device__ __forceinline__ void add(float v, uint32_t* shist) {
     const int bin = (int)(__float_as_uint(v) >> 21);
     const unsigned o = (unsigned)(bin - base);
     if (o < 8u)
-      packed += (uint64_t)w << (8u * o);
+      packed += 1ull << (8u * o);
     else
-      atomicAdd(&shist[bin], w);
+      atomicAdd(&shist[bin], weight);
   }
   __device__ __forceinline__ void flush(uint32_t* shist) {
     const int lane = threadIdx.x & 63;
@@ -44,7 +52,7 @@ struct WindowHist {
       for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
       const int bin = base + o;
       if (lane == 0 && c > 0 && bin >= 0 && bin < DSVGD_RADIX_BINS)
-        atomicAdd(&shist[bin], (uint32_t)c);
+        atomicAdd(&shist[bin], (uint32_t)c * weight);
     }
   }
 };
@@ -56,13 +64,13 @@ __device__ __forceinline__ void flush_block_hist(const uint32_t* shist, dsvgd_se
   }
 }
 
-// histogram of a lane's NV values (+inf = invalid, skipped), weight w
+// histogram of a lane's NV values (+inf = invalid, skipped), at wh's weight
 template <int NV>
-__device__ __forceinline__ void hist_account(WindowHist& wh, const float (&v)[NV], uint32_t w,
+__device__ __forceinline__ void hist_account(WindowHist& wh, const float (&v)[NV],
                                              uint32_t* shist) {
 #pragma unroll
   for (int i = 0; i < NV; ++i)
-    if (v[i] != INFINITY) wh.add(v[i], w, shist);
+    if (v[i] != INFINITY) wh.add(v[i], shist);
 }
 
 __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t x, uint32_t& total) {

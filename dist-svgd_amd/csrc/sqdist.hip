@@ -120,8 +120,8 @@ __device__ __forceinline__ void sq_epilogue(Tile& tile, int bi, int bj, int64_t 
               f32x4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
       }
       if (smode == kSelHist) {
-        if (mi == 0 && ni == 0) wh.init(v[0]);
-        hist_account(wh, v, weight, shist);
+        if (mi == 0 && ni == 0) wh.init(v[0], weight);
+        hist_account(wh, v, shist);
       } else if (smode == kSelBracket) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -192,8 +192,8 @@ __device__ __forceinline__ void sq_epilogue16(Tile& tile, int bi, int bj, int64_
         *reinterpret_cast<f32x4*>(Dmir + ((rbase >> 4) + mt) * kPanelElems + (int64_t)cl * 16 +
                                   g4) = f32x4{v[0], v[1], v[2], v[3]};
       if (smode == kSelHist) {
-        if (mt == 0 && nt == 0) wh.init(v[0]);
-        hist_account(wh, v, weight, shist);
+        if (mt == 0 && nt == 0) wh.init(v[0], weight);
+        hist_account(wh, v, shist);
       } else if (smode == kSelBracket) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) sw.add(v[r]);
@@ -799,7 +799,7 @@ __global__ __launch_bounds__(256) void sqdist_direct_kernel(const float* __restr
   }
   WindowHist wh;
   if (smode == kSelHist)
-    wh.init((i0 + ty * 8 < m && j0 + tx * 8 < n) ? acc[0][0] : INFINITY);
+    wh.init((i0 + ty * 8 < m && j0 + tx * 8 < n) ? acc[0][0] : INFINITY, 1u);
   const int64_t nslots = (int64_t)gridDim.x * gridDim.y * 4;
   const int64_t slot = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (t >> 6);
   SlotWriter sw;
@@ -821,7 +821,7 @@ __global__ __launch_bounds__(256) void sqdist_direct_kernel(const float* __restr
     *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
     *reinterpret_cast<f32x4*>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
     if (smode == kSelHist) {
-      hist_account(wh, v, 1u, shist);
+      hist_account(wh, v, shist);
     } else if (smode == kSelBracket) {
 #pragma unroll
       for (int b = 0; b < 8; ++b) sw.add(v[b]);
