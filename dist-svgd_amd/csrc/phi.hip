@@ -1301,9 +1301,15 @@ int dsvgd_phi_set_symrow(int on) {
 // the B operand's leading dimension ldb (w: the one-operand form's dp), the
 // alignment, the grid limits and the row block.  0 (ldd is then n_pad), or
 // the error code.
+// rows_walk: the launch is phi_w1's one-launch symmetric walk (DS 4), which
+// takes no empty split-K slice: a slice that starts past K (kb0 > K) would
+// have a plain phase of (kb0 - K) / 16 K-steps from K on -- loads past the
+// block's D panel row and past the image.  Every other form leaves an empty
+// slice as exact zeros without a load (NNTile / NNX3Tile::run return on
+// k0 >= k1, phi_w1's phase on nsteps <= 0).
 static int phi_mm_check(bool ptrs, const void* D, const void* B, int64_t ldd, int64_t ldb,
                         int64_t ldk, int64_t row0, int64_t m, int64_t n, int64_t splits,
-                        bool w = false) {
+                        bool w = false, bool rows_walk = false) {
   DSVGD_REQUIRE(ptrs, "null pointer");
   DSVGD_REQUIRE(m > 0 && n > 0, "sizes");
   DSVGD_REQUIRE(ldd == roundup(n, 128), "ldd must equal roundup(n,128) (panel layout)");
@@ -1316,6 +1322,12 @@ static int phi_mm_check(bool ptrs, const void* D, const void* B, int64_t ldd, in
   DSVGD_REQUIRE(roundup(m, 128) / 128 <= 65535, "too many row tiles");
   DSVGD_REQUIRE(splits >= 1 && splits <= 1024, "splits must be in [1, 1024]");
   DSVGD_REQUIRE(row0 >= 0 && row0 + m <= n, "row block outside [0, n)");
+  if (rows_walk) {
+    const int64_t K = roundup(n, 128), kchunk = roundup((K + splits - 1) / splits, kX3Step);
+    DSVGD_REQUIRE((splits - 1) * kchunk < K,
+                  "splits: the symmetric layout's one-launch form takes no empty split-K slice "
+                  "((splits - 1) * roundup(ceil(n_pad / splits), 16) must stay below n_pad)");
+  }
   return 0;
 }
 
@@ -1408,8 +1420,10 @@ int dsvgd_phi_mm_h2_kern(const float* D, int64_t ldd, const void* Yh, int64_t ld
                          float* KY, int64_t ldk, float* rowsum, int sym, const float* colinv,
                          const float* gate, dsvgd_kernel kern, int order, void* stream) {
   DSVGD_REQUIRE_KERN(kern, order);
+  // (launch_nn_x3's condition for phi_w1 DS 4)
+  const bool rows_walk = sym && ldy % 512 == 0 && splits >= 2 && g_phi_symrow;
   if (int rc = phi_mm_check(D && Yh && st && KY && rowsum && colinv, D, Yh, ldd, ldy, ldk, row0, m,
-                            n, splits))
+                            n, splits, false, rows_walk))
     return rc;
   DSVGD_REQUIRE(ldd * ldy * 4 < ((int64_t)1 << 31) && ldd * 128 * 4 < ((int64_t)1 << 31),
                 "n x ldy too large for 32-bit buffer offsets (use dsvgd_phi_mm_kern)");
@@ -1433,7 +1447,7 @@ int dsvgd_phi_mm_h2w(const float* D, int64_t ldd, const void* Wh, int64_t ldw, i
                      int64_t ldk, float* rowsum, int sym, const float* colinv, const float* gate,
                      void* stream) {
   if (int rc = phi_mm_check(D && Wh && st && KW && rowsum && colinv, D, Wh, ldd, ldw, ldk, row0, m,
-                            n, splits, true))
+                            n, splits, true, sym != 0))
     return rc;
   DSVGD_REQUIRE(ldd * ldw * 4 < ((int64_t)1 << 31) && ldd * 128 * 4 < ((int64_t)1 << 31),
                 "n x ldw too large for 32-bit buffer offsets");

@@ -231,7 +231,16 @@ int dsvgd_sqdist_x3(const void* Yg, const float* norms, int64_t row0, int64_t m,
  * slice z at KY + z*m*ldk), rowsum splits x roundup(m,128) floats.
  * Replaces the inner loop of dsvgd/sampler.py:35-40 (_phi_hat) and
  * dsvgd/distsampler.py:84-101.  dsvgd_phi_splits gives a slice count that
- * fills the 256 CUs (>= 2 blocks per CU) for an m-row block. */
+ * fills the 256 CUs (>= 2 blocks per CU) for an m-row block.
+ * Slice z covers the columns [z kchunk, min(n_pad, (z + 1) kchunk)), kchunk =
+ * roundup(ceil(n_pad / splits), 16) (32 on the f32 engine).  `splits` is the
+ * caller's: a slice past n_pad (z kchunk >= n_pad) is EMPTY and comes out as
+ * exact zeros -- except in the symmetric layout's one-launch form
+ * (dsvgd_phi_mm_h2 with sym = 1, ldy % 512 == 0, splits >= 2 under symrow 1,
+ * and dsvgd_phi_mm_h2w with sym = 1), whose walk would step past n_pad there:
+ * these refuse (splits - 1) kchunk >= n_pad with an error and launch nothing.
+ * (The two-launch hybrid has no kchunk: it deals the 16-column K-steps out
+ * round-robin, and a slice that gets none is exact zeros.) */
 int64_t dsvgd_phi_splits(int64_t m, int64_t n, int64_t ldy);
 /* The symmetric layout's phi_mm form (A/B switch, returns the previous
  * setting): 1 (default) = one launch, each row block's split-K slices walking
